@@ -12,15 +12,21 @@ client: weak scaling) and each step ends with an RCCL gather of the averaged
 shards to rank 0 over xGMI (the response vector is assembled on the root).
 
 Output: ONE compact JSON line, the last line of stdout (≤ 4 KB: the driver parses it
-from an 8 KB tail), holding the contract keys, the roofline of the dominant kernel, a
-bounded CPU-baseline sample of the oracle (the C restatement of the enclave's
-`baseline`, 1 thread), the host-inclusive ECALL rate, the metric's literal MLP-MNIST
-config and one-number summaries of the other BASELINE.json configs.  Everything the
-legs measured in full (per-kernel blocks, exp5's 40 rows, reference_configs, the
-per-config CPU baselines, the multi-GPU legs) goes to the detail file the line names
-(`--detail`, default gpurun_out/bench_detail.json); the legs live in bench_legs.py.
+from an 8 KB tail).  A plain run sets up, warms up, times the K steps and prints the
+contract keys with the roofline the timed launches themselves give.  `--full` adds
+every other leg: a bounded CPU-baseline sample of the oracle (the C restatement of the
+enclave's `baseline`, 1 thread), the host-inclusive ECALL rate, the metric's literal
+MLP-MNIST config and one-number summaries of the other BASELINE.json configs (N > 1:
+the sharded and C-ABI multi-GPU legs).  Everything those legs measured in full
+(per-kernel blocks, exp5's 40 rows, reference_configs, the per-config CPU baselines,
+the multi-GPU legs) goes to the detail file the line names (`--detail`, with `--full`
+bench_out/bench_detail.json unless given); the legs live in bench_legs.py.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ns] [--no-extra]
+`--dump-outputs DIR` writes what the last timed step computed (the averaged aggregate a
+caller of the timed path receives) to DIR/aggregate.npy as float32; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ns] [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -176,12 +182,38 @@ def emit(full, detail_path):
     print(s, flush=True)
 
 
-def main():
+DUMP_MAX_BYTES = 64 * 2 ** 20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(path_dir, arrays):
+    """Write each array of `arrays` (name -> float ndarray) as path_dir/<name>.npy, float32
+    or float64, at most DUMP_MAX_BYTES in all: a larger output is cut down to a fixed,
+    seeded sample of its elements (sorted positions, the same for every run)."""
+    os.makedirs(path_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        if a.nbytes > budget:
+            keep = budget // a.itemsize - 32  # the .npy header
+            pos = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(path_dir, name + ".npy"), a)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="ns", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (CPU baselines, host-inclusive ECALLs, the "
+                         "other configs, the reference's tables, the multi-GPU legs) and write "
+                         "the detail file; a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     ap.add_argument("--no-extra", action="store_true", help="skip the other configs")
     ap.add_argument("--extra", default="mnist30,mnist100,c1,c3,c4,c5")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -189,9 +221,17 @@ def main():
     ap.add_argument("--no-cpu-configs", action="store_true",
                     help="skip the per-config CPU baseline (about a minute of CPU)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-inclusive ECALL leg")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="where the full results go (the stdout line is a summary)")
-    args = ap.parse_args()
+    ap.add_argument("--detail", default=None,
+                    help="where the full results go (the stdout line is a summary); with --full "
+                         "bench_out/bench_detail.json unless given, \"\" for none")
+    args = ap.parse_args(argv)
+    if args.detail is None and args.full:
+        args.detail = os.path.join(ROOT, "bench_out", "bench_detail.json")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     import torch
     import torch.distributed as dist
@@ -284,6 +324,12 @@ def main():
     ms = elapsed / args.steps * 1e3
     value = world * n * kk / (elapsed / args.steps)
     algo_bytes = n * kk * 8 + d * 4  # records read + averaged output written, per launch
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # what the last timed step handed its caller: the averaged aggregate (N > 1: the
+        # shards as gathered on rank 0, in rank order)
+        b = (args.warmup + args.steps - 1) % 2
+        last = torch.cat(gathered[b]) if world > 1 else outs[b]
+        dump_outputs(args.dump_outputs, {"aggregate": last.cpu().numpy()})
     del recs, gathered
     full = None
     if rank == 0:
@@ -312,7 +358,7 @@ def main():
                          "rocprof_avg_us": rp["avg_us"] if rp else None,
                          "rocprof_source": rp["source"] if rp else None},
         }
-    if world > 1 and not args.no_extra:
+    if world > 1 and args.full and not args.no_extra:
         # Every sharded leg runs under a watchdog: if the legs overrun the budget (a stuck
         # collective), rank 0 prints the line with what finished and every rank exits, so
         # the headline measurement above is never lost to an extra.
@@ -376,11 +422,12 @@ def main():
         return
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        one = world == 1 and args.full  # the legs beside the headline: --full only
+        if one and not args.no_cpu_baseline:
             full["cpu_baseline"] = cpu_baseline_sample(d, n, args.cpu_seconds)
-        if world == 1 and not args.no_e2e and k is None:
+        if one and not args.no_e2e and k is None:
             full["e2e_host_inclusive"] = e2e_sample(torch, D, n, d, device)
-        if world == 1 and not args.no_extra:
+        if one and not args.no_extra:
             full["extra"] = run_config_legs(torch, D, device, args)
             # the metric's literal configuration (100 clients x MLP-MNIST, dense baseline),
             # inputs rotated through > 1.5 x the Infinity Cache so every launch reads HBM;

@@ -26,7 +26,7 @@ for spec in ${ABH:+"$ABH"}; do
   echo "abh $w $hook"
 done
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 600 python -u bench.py ${BENCH_ARGS} --detail "$OUT/bench_detail.json" > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 12
+  timeout -k 10 600 python -u bench.py --full ${BENCH_ARGS} --detail "$OUT/bench_detail.json" > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 12
   tail -c 600 "$OUT/bench.json"; echo
 fi
 for w in ${PROFILE}; do

@@ -284,9 +284,31 @@ def config_aggregate_fixtures(utils, update, models):
     np.savez_compressed(os.path.join(OUT, "ref_aggregate_cfg.npz"), **flat)
 
 
+AES_REF_CASES = [(0, 1), (5, 15), (17, 16), (99, 1000), (65535, 4097), (70000, 8 * 5089)]
+
+
+def aes_reference_fixtures():
+    """sgx_aes_ctr_encrypt of the reference's own AES library (oracle/_ref) under the
+    session keys of a few client ids, on random bytes of lengths around the 16-B block:
+    plaintexts and ciphertexts stored back to back, so tests/test_oracle.py pins the
+    oracle's AES to the reference's where oracle/_ref cannot be built."""
+    rng = np.random.default_rng(7)
+    pt = [rng.integers(0, 256, ln, dtype=np.uint8) for _, ln in AES_REF_CASES]
+    ct = [np.frombuffer(O.ref_aes_ctr_encrypt(O.session_key(cid), p.tobytes()), np.uint8)
+          for (cid, _), p in zip(AES_REF_CASES, pt)]
+    np.savez_compressed(os.path.join(OUT, "aes_ref_ctr.npz"),
+                        client_ids=np.array([c for c, _ in AES_REF_CASES], dtype=np.uint32),
+                        lengths=np.array([ln for _, ln in AES_REF_CASES], dtype=np.int64),
+                        plaintext=np.concatenate(pt), ciphertext=np.concatenate(ct))
+    print("aes_ref_ctr", sum(ln for _, ln in AES_REF_CASES), "bytes")
+
+
 def main():
     if "--wire-only" in sys.argv:
         wire_fixtures()
+        return
+    if "--aes-only" in sys.argv:
+        aes_reference_fixtures()
         return
     utils, update, models = import_reference()
     if "--client-only" in sys.argv:
@@ -380,6 +402,7 @@ def main():
     np.savez_compressed(os.path.join(OUT, "ffi_test_kat.npz"), plaintext=np.frombuffer(src, np.uint8),
                         ciphertext=np.frombuffer(ct, np.uint8))
     print("ffi kat ok")
+    aes_reference_fixtures()
     client_fixtures(utils, update, models)
     reference_aggregate_fixtures(utils, update, models)
     config_aggregate_fixtures(utils, update, models)

@@ -92,6 +92,37 @@ def test_unwritable_detail_still_prints(capsys):
     assert line["detail"].startswith("not written")
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    """A plain run has no detail file and none of the other legs; --full names the detail
+    file unless one is given."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.detail, a.dump_outputs) == (7, 2, False, None, None)
+    f = bench.parse_args(["--full"])
+    assert f.full and f.detail.endswith(os.path.join("bench_out", "bench_detail.json"))
+    assert bench.parse_args(["--full", "--detail", "x.json"]).detail == "x.json"
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float_npy_within_the_cap(tmp_path, monkeypatch):
+    import numpy as np
+    small = np.arange(1000, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "o"), {"aggregate": small})
+    got = np.load(tmp_path / "o" / "aggregate.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    # over the cap: a fixed, seeded sample, the same positions on every call
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2048)
+    big = np.random.default_rng(3).normal(size=5000)
+    bench.dump_outputs(str(tmp_path / "p"), {"x": big, "y": big.astype(np.float32)})
+    bench.dump_outputs(str(tmp_path / "q"), {"x": big, "y": big.astype(np.float32)})
+    total = 0
+    for name, dt in (("x", np.float64), ("y", np.float32)):
+        p, q = np.load(tmp_path / "p" / f"{name}.npy"), np.load(tmp_path / "q" / f"{name}.npy")
+        assert p.dtype == dt and np.array_equal(p, q) and 0 < p.size < big.size
+        assert np.isin(p, big.astype(dt)).all()
+        total += os.path.getsize(tmp_path / "p" / f"{name}.npy")
+    assert total <= 2048
+
+
 def test_rocprof_cross_check_reads_the_newest_round():
     """bench_legs.rocprof_kernel takes the newest committed rocprofv3 summary of a config
     (VERDICT r5 #6: it read round 4's while round 5's existed)."""

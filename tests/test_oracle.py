@@ -68,14 +68,23 @@ def test_fips197_block(oracle):
     assert pt  # (block KAT for the device tables lives in test_abi.py)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLDEN), "..", "oracle", "_ref",
-                                                    "libsgx_enc.so")), reason="oracle/_ref not built")
 def test_aes_matches_reference_library(oracle):
-    rng = np.random.default_rng(7)
-    for cid, ln in [(0, 1), (5, 15), (17, 16), (99, 1000), (65535, 4097), (70000, 8 * 5089)]:
-        data = rng.integers(0, 256, ln, dtype=np.uint8).tobytes()
+    # tests/golden/aes_ref_ctr.npz: the reference library's own ciphertexts of these
+    # inputs (make_fixtures.py aes_reference_fixtures), so the pin holds where oracle/_ref
+    # is not built; where it is, the library itself is asked as well
+    fx = load("aes_ref_ctr")
+    cases = [(0, 1), (5, 15), (17, 16), (99, 1000), (65535, 4097), (70000, 8 * 5089)]
+    assert [(int(c), int(ln)) for c, ln in zip(fx["client_ids"], fx["lengths"])] == cases
+    off = 0
+    for cid, ln in cases:
+        data = fx["plaintext"][off:off + ln].tobytes()  # default_rng(7) bytes, as before
+        assert len(data) == ln
         key = oracle.session_key(cid)
-        assert oracle.aes128_ctr(key, data) == oracle.ref_aes_ctr_encrypt(key, data)
+        ct = oracle.aes128_ctr(key, data)
+        assert ct == fx["ciphertext"][off:off + ln].tobytes()
+        if oracle.ref_aes_available():
+            assert ct == oracle.ref_aes_ctr_encrypt(key, data)
+        off += ln
 
 
 @pytest.mark.parametrize("name", ["mnist_sparse", "mnist_sparse_clip"])
