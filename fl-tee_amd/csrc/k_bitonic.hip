@@ -33,126 +33,40 @@
 
 #include "common.h"
 
-// A/B switches of the tile kernels' code shape (compile time; scripts/ab_build.sh):
-//   FLTEE_CE_BATCH   a step's swap decisions all computed before its selects
-//   FLTEE_LDS_BATCH  groups per batch of a round's LDS reads issued before their
-//                    compare-exchanges and writes (0: all of the lane's groups)
-#ifndef FLTEE_CE_BATCH
-#define FLTEE_CE_BATCH 1
-#endif
-#ifndef FLTEE_LDS_BATCH
-#define FLTEE_LDS_BATCH 2
-#endif
-//   FLTEE_KEY_AFTER_DATA  the keyed comparator's step keys computed after each round's loads
-#ifndef FLTEE_KEY_AFTER_DATA
-#define FLTEE_KEY_AFTER_DATA 1
-#endif
-//   FLTEE_KEYED_SPLIT  the keyed comparator as one per-lane product per step + a scalar
-//                      (off: it moves the cost to the scalar unit, C4 8.93 vs 9.01 ms with
-//                      it, `profiles/r03/ab/ab6_c4.jsonl`)
-#ifndef FLTEE_KEYED_SPLIT
-#define FLTEE_KEYED_SPLIT 0
-#endif
-//   FLTEE_KEYED_DIRFOLD  the keyed comparator with the direction folded into the hashed word
-//                        (keyed_swap; off: the round-3 form, for A/B)
-#ifndef FLTEE_KEYED_DIRFOLD
-#define FLTEE_KEYED_DIRFOLD 1
-#endif
+// Code-shape variants measured in rounds 2-6 and settled (one line each; the losing arms
+// left the source, DESIGN.md names the last tree that carries them):
+//   a step's swap decisions all computed before its selects (kept), LDS reads kept from
+//     pairing into ds_read2_b64 (rejected), other read batch sizes (rejected):
+//     `profiles/r04/ab/ab24_lds_batch_read1_ce_batch_rejected.jsonl`
+//   the keyed comparator's step keys computed after each round's loads (after_data; kept,
+//     `profiles/r03/ab/`)
+//   the keyed comparator as a per-lane product + a scalar constant: C4 9.01 vs 8.93 ms,
+//     rejected (`profiles/r03/ab/ab6_c4.jsonl`)
+//   the keyed comparator from a per-step table of scalar-loaded constants: C4 8.45 vs 7.85
+//     ms, rejected (`profiles/r05/ab/ab5_keyed_table_c4_rejected.jsonl`)
+//   the first pass's stages inside a wave's records without block barriers, and a stage
+//     above them split where that adds no LDS round: C4's first pass 1,085 -> 1,065 us
+//     (kept; always splitting is slower, `profiles/r04/ab/ab6_wave_split.jsonl`)
+//   the tile passes load and store 16-B slot pairs (kept); the contiguous direct merges
+//     too: only the selecting pass gains, 552 -> 517 us, the plain merges lose 251 -> 279
+//     us (`profiles/r04/ab/ab9_merge_pairs_*.jsonl`)
+//   the first pass over 2^14 tiles as 512 lanes x 32 records: 1,640 vs 1,068 us at C4,
+//     rejected (`profiles/r04/ab/ab12_first_pass_e32_rejected_*.jsonl`); C3's 2^12 tiles as
+//     256 lanes x 16: 24.0 vs 21.0 us, rejected (`ab14_first_pass_256x16_c3_rejected.jsonl`)
+//   the selecting pass storing every record, the unselected ones out of range: 530 vs 520
+//     us, rejected (`profiles/r04/ab/ab10_sel_store_oob_c4.jsonl`)
+//   compile-time tail rounds for the keyed shuffle too: C4 8.00 -> 7.89 ms (kept;
+//     `profiles/r04/ab/ab18_keyed_tail_ct_c4.jsonl`), and for the 1024-lane tiles with rows
+//     of 2^10: C4 7.90 -> 7.84 ms (kept; `profiles/r04/ab/ab19_tile_w10_*.jsonl`)
+//   strided tiles on rows of 8 records (64-B segments): C5 12.29 -> 13.65 ms, rejected
+//     (`profiles/r05/ab/ab14_tile_rows_of_8_rejected.jsonl`)
+//   a tile pass's block on its last tile prefetches nothing: C3 0.1295 -> 0.1285 ms (kept;
+//     `profiles/r05/ab/ab21_*`)
+
+// Groups per batch of a round's LDS reads issued before their compare-exchanges and writes
+// (`profiles/r04/ab/ab24_lds_batch_read1_ce_batch_rejected.jsonl`)
 template <int G>
-constexpr int kLdsBatch = (FLTEE_LDS_BATCH == 0 || FLTEE_LDS_BATCH > G) ? G : FLTEE_LDS_BATCH;
-//   FLTEE_LDS_READ1   LDS reads as single ds_read_b64 (no ds_read2_b64 pairing)
-#ifndef FLTEE_LDS_READ1
-#define FLTEE_LDS_READ1 0
-#endif
-//   FLTEE_TILE_HEADREG  a strided tile's first row round on its prefetch registers
-#ifndef FLTEE_TILE_HEADREG
-#define FLTEE_TILE_HEADREG 1
-#endif
-//   FLTEE_TAIL_CT_1024  compile-time tail rounds in the 1024-lane strided tiles too
-#ifndef FLTEE_TAIL_CT_1024
-#define FLTEE_TAIL_CT_1024 1
-#endif
-//   FLTEE_PLAN_SHUFFLE  the keyed shuffle (mode 2) on the planned schedule too
-#ifndef FLTEE_PLAN_SHUFFLE
-#define FLTEE_PLAN_SHUFFLE 1
-#endif
-//   FLTEE_TID_FRESH   the lane id re-read per LDS round (see lane_tid)
-#ifndef FLTEE_TID_FRESH
-#define FLTEE_TID_FRESH 1
-#endif
-//   FLTEE_WAVE_LOCAL  the first pass's stages inside a wave's records without block barriers
-#ifndef FLTEE_WAVE_LOCAL
-#define FLTEE_WAVE_LOCAL 1
-#endif
-//   FLTEE_WAVE_SPLIT  the first pass's stages above log2(64 E): the steps that cross waves
-//   block-wide, then the stage's steps inside a wave's records wave-local (1: always;
-//   2: only where the split adds no LDS round; 0: the whole stage block-wide).  A/B
-//   (`profiles/r04/ab/ab6_wave_split.jsonl`): 2 takes C4's first pass 1,085 -> 1,065 us and
-//   C5's 1,234 -> 1,227 us; 1 is slower than 0 (the extra rounds cost more than the barriers)
-#ifndef FLTEE_WAVE_SPLIT
-#define FLTEE_WAVE_SPLIT 2
-#endif
-//   FLTEE_TILE_PAIRS  the compile-time-shaped tile passes load and store slot pairs (16 B
-//   per lane: lane t holds tile elements 2t, 2t + 1 (+ 2 NT r)) instead of single records
-#ifndef FLTEE_TILE_PAIRS
-#define FLTEE_TILE_PAIRS 1
-#endif
-//   FLTEE_MERGE_PAIRS  the same for the contiguous direct merges (bitonic_merge_direct):
-//   1 all, 2 the selecting last pass of nips19's shuffle only, 0 none.  A/B
-//   (`profiles/r04/ab/ab9_merge_pairs_*.jsonl`): the selecting pass 552 -> 517 us, the
-//   plain merges 251 -> 279 us (C4) / 335 -> 364 us (C5) — their last round then stores
-//   groups of 8 instead of 4
-#ifndef FLTEE_MERGE_PAIRS
-#define FLTEE_MERGE_PAIRS 2
-#endif
-// (Measured and removed, round 4: the first pass over 2^14 tiles as 512 lanes x 32 records —
-// 5 steps per LDS round, stages 1..5 in registers — 1,640 vs 1,068 us at C4, 1,821 vs 1,220
-// at C5: the compile-time rounds spill at 32 records per lane and the runtime ones run
-// slower; `profiles/r04/ab/ab12_first_pass_e32_rejected_*.jsonl`.  Likewise C3's 2^12 tiles as
-// 256 lanes x 16: 24.0 vs 21.0 us, `ab14_first_pass_256x16_c3_rejected.jsonl`.)
-//   FLTEE_SEL_STORE_OOB  the selecting pass stores every record, the unselected ones out of
-//   the tile's buffer range (dropped), instead of a branch per record (A/B: 530 vs 520 us,
-//   not kept; `profiles/r04/ab/ab10_sel_store_oob_c4.jsonl`)
-//   FLTEE_TAIL_CT_KEYED  compile-time tail rounds for the keyed shuffle (mode 2) too (round 4:
-//   no spills since the 1024-lane tiles lost theirs; C4 8.00 -> 7.89 ms, bit-identical,
-//   `profiles/r04/ab/ab18_keyed_tail_ct_c4.jsonl`)
-#ifndef FLTEE_TAIL_CT_KEYED
-#define FLTEE_TAIL_CT_KEYED 1
-#endif
-//   FLTEE_TILE_W10  compile-time rounds for the 1024-lane strided tiles with rows of 2^10 too
-//   (the planned passes with a 10-step tail; round 4: C4 7.90 -> 7.84 ms, C5 unchanged,
-//   `profiles/r04/ab/ab19_tile_w10_*.jsonl`)
-#ifndef FLTEE_TILE_W10
-#define FLTEE_TILE_W10 1
-#endif
-//   FLTEE_TILE_MINW14  the narrowest rows (log2 records) of a planned strided 2^14 tile: 4
-//   (128-B row segments) or 3 (64-B segments: 11 row steps per pass; the plan may then use
-//   rows of 2^8 too, compiled with it).  At M = 2^27 the plan drops from 23 to 22 launches,
-//   but the passes on 64-B rows run far slower (round 5, bit-identical: C5 12.29 -> 13.65
-//   ms, C4 7.85 -> 8.45 ms; tile passes 367 -> 447 us on average,
-//   `profiles/r05/ab/ab14_tile_rows_of_8_rejected.jsonl`), so 4 stays.
-//   FLTEE_TILE_SKIP_SELF  a tile pass's block on its last tile prefetches nothing (round 5,
-//   bit-identical: C3 0.1295 -> 0.1285 ms, C4 / C5 unchanged, `profiles/r05/ab/ab21_*`)
-#ifndef FLTEE_TILE_SKIP_SELF
-#define FLTEE_TILE_SKIP_SELF 1
-#endif
-#ifndef FLTEE_TILE_MINW14
-#define FLTEE_TILE_MINW14 4
-#endif
-//   FLTEE_TILE_MINW12  the same for the 512-lane 2^12 tiles (M <= 2^20: C3 13 -> 12 launches,
-//   0.1365 -> 0.1387 ms, same record)
-#ifndef FLTEE_TILE_MINW12
-#define FLTEE_TILE_MINW12 4
-#endif
-#ifndef FLTEE_DIRECT_MERGE
-#define FLTEE_DIRECT_MERGE 0
-#endif
-#ifndef FLTEE_UNSW_TILES
-#define FLTEE_UNSW_TILES 1
-#endif
-#ifndef FLTEE_SEL_STORE_OOB
-#define FLTEE_SEL_STORE_OOB 0
-#endif
+constexpr int kLdsBatch = 2 > G ? G : 2;
 
 namespace fltee {
 
@@ -178,17 +92,6 @@ __device__ __forceinline__ uint32_t after_data(uint32_t s, uint32_t v) {
     return s;
 }
 
-// The keyed comparator (MODE 2) split into a per-lane and a wave-uniform part.  For a
-// group whose first position p0 has zero bits where dq = q << dlog has ones, l = p0 + dq
-// = p0 ^ dq, so l ^ key = x ^ dq = x + dq - 2 (key & dq) with x = p0 ^ key, and
-//   (l ^ key) * K = x * K + (dq - 2 (key & dq)) * K   (mod 2^32):
-// the top bit cond2<2> takes is the sign of X + C(dq), X = x * K once per group and step,
-// C(dq) computed by the scalar unit.  One v_add per compare instead of an add, a xor and
-// a v_mul_lo_u32; the same bits.
-__device__ __forceinline__ uint32_t keyed_c(uint32_t key, uint32_t dq) {
-    return (dq - 2u * (key & dq)) * 0x9E3779B1u;
-}
-
 // The keyed comparator (MODE 2) with the block's direction folded into the hashed word.
 // swap = asc ^ top bit of ((l ^ key) * K).  For S in {0, 2^31}: (y ^ S) * K = y * K + S
 // (mod 2^32; K odd), so the top bit of ((l ^ key ^ S) * K) is that of (l ^ key) * K,
@@ -202,76 +105,6 @@ __device__ __forceinline__ bool keyed_swap(uint32_t kb, uint32_t dq) {
     return (int32_t)((kb ^ dq) * 0x9E3779B1u) < 0;
 }
 
-// The keyed comparator read from a table (round 5, FLTEE_KEYED_TABLE).  With kb = p0 ^
-// dir ^ key and dq = q << dlog (p0 has zeros at dq's bits, dq < 2^31): kb & dq = key & dq,
-// so (kb ^ dq) * K = kb * K + C(dq) with C(dq) = keyed_c(key, dq) — one product per group
-// and step (X) and, per compare-exchange, one v_add of a per-(step, q) constant and the
-// sign test, instead of a v_xor, a half-rate v_mul_lo_u32 and the sign test: 6 VALU issue
-// slots per compare-exchange instead of 9.  The constants of every step a network can run
-// — T[ilog][jlog][lv][q] = keyed_c(step_key(seed, ilog, jlog), q << (jlog - lv)), the
-// group's steps lv = 0..3 at distance 2^(jlog - lv) — sit in a per-device table of 256 KB
-// built for the network's seed before its first pass (keyed_table_prepare, stream-
-// ordered), and a step's 16 constants come in as one scalar load (s_load_dwordx16) into
-// SGPRs: no VALU, no LDS.  Every address is a function of (ilog, jlog, lv) — public — and
-// the bits are the same (a ring identity mod 2^32).  Groups of more than 16 records (the
-// register passes of 5 and 6 steps) keep the direct form.
-// Measured and REJECTED (off by default): C4 8.45 vs 7.85 ms, bit-identical
-// (`profiles/r05/ab/ab5_keyed_table_c4_rejected.jsonl`).  The asm has a quarter of the
-// multiplies (222 vs 846 v_mul_lo_u32 in the first pass), but every scalar load is counted
-// in the same lgkm counter as the LDS reads and returns out of order, so each use of a row
-// waits for ALL outstanding LDS reads (lgkmcnt(0): 116 such waits in the pass against 63
-// in the index sort's) — the LDS rounds lose their overlap.
-#ifndef FLTEE_KEYED_TABLE
-#define FLTEE_KEYED_TABLE 0
-#endif
-__device__ const uint32_t *g_keyed_tab;  // this device's table (set once per device)
-typedef __attribute__((address_space(4))) const uint32_t kt_u32;  // scalar (constant) loads
-__device__ __forceinline__ const kt_u32 *keyed_row(uint32_t ilog, uint32_t jlog, uint32_t lv) {
-    return (const kt_u32 *)g_keyed_tab + ((((ilog & 31u) << 5) | (jlog & 31u)) * 4u + lv) * 16u;
-}
-constexpr uint32_t kKeyedTabEntries = 32u * 32u * 4u * 16u;
-
-__global__ void keyed_table_kernel(uint32_t *__restrict__ tab, uint32_t seed) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= kKeyedTabEntries) return;
-    const uint32_t q = i & 15u, lv = (i >> 4) & 3u, jlog = (i >> 6) & 31u, ilog = i >> 11;
-    uint32_t c = 0;
-    if (lv <= jlog) c = keyed_c(shuffle_step_key(seed, ilog, jlog), q << (jlog - lv));
-    tab[i] = c;
-}
-
-struct KeyedTab {
-    uint32_t *ptr = nullptr;
-    uint32_t seed = 0;
-    bool valid = false;
-};
-static KeyedTab g_kt[64];
-
-// the table for `seed` on the current device, ahead of the network's launches on s (a
-// device's networks run on one stream at a time: the library's calls are serialised)
-static hipError_t keyed_table_prepare(uint32_t seed, hipStream_t s) {
-    if (!FLTEE_KEYED_TABLE) return hipSuccess;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess || dev < 0 || dev >= 64) return e != hipSuccess ? e : hipErrorInvalidDevice;
-    KeyedTab &t = g_kt[dev];
-    if (!t.ptr) {
-        e = hipMalloc(&t.ptr, kKeyedTabEntries * 4);
-        if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_keyed_tab), &t.ptr, sizeof(t.ptr));
-        if (e != hipSuccess) {
-            t.ptr = nullptr;
-            return e;
-        }
-        t.valid = false;
-    }
-    if (t.valid && t.seed == seed) return hipSuccess;
-    FLTEE_LAUNCH(keyed_table_kernel, dim3(kKeyedTabEntries / 256), dim3(256), 0, s, t.ptr, seed);
-    e = hipGetLastError();
-    t.seed = seed;
-    t.valid = e == hipSuccess;
-    return e;
-}
-
 // Run steps lv = R-1..0 (distance 2^(dlog+lv)) of stage ilog on one group of 2^R
 // records held in v[], whose first record sits at global position p0.  The group
 // spans 2^(dlog+R) <= 2^ilog aligned positions, so the direction bit (l & i) == 0
@@ -279,25 +112,17 @@ static hipError_t keyed_table_prepare(uint32_t seed, hipStream_t s) {
 template <int MODE, int R>
 __device__ __forceinline__ void group_steps(uint64_t (&v)[1 << R], uint32_t p0, uint32_t dlog,
                                             uint32_t ilog, uint32_t seed) {
-    if constexpr (MODE == 2 && FLTEE_KEY_AFTER_DATA) seed = after_data(seed, (uint32_t)v[0]);
+    if constexpr (MODE == 2) seed = after_data(seed, (uint32_t)v[0]);
     const bool asc = (p0 & (1u << ilog)) == 0;
     const uint32_t pdir = MODE == 2 ? p0 ^ keyed_dir(asc) : 0u;
 #pragma unroll
     for (int lv = R - 1; lv >= 0; --lv) {
         const uint32_t key = MODE == 2 ? shuffle_step_key(seed, ilog, dlog + lv) : 0u;
-        const uint32_t X = (MODE == 2 && FLTEE_KEYED_SPLIT) ? (p0 ^ key) * 0x9E3779B1u : 0u;
         const uint32_t kb = pdir ^ key;
-        constexpr bool kTab = MODE == 2 && FLTEE_KEYED_TABLE && R <= 4;
-        const uint32_t XT = kTab ? kb * 0x9E3779B1u : 0u;
-        const kt_u32 *row = kTab ? keyed_row(ilog, dlog + (uint32_t)lv, (uint32_t)lv) : nullptr;
         auto decide = [&](int q, int qm) -> bool {
-            if constexpr (kTab) return (int32_t)(XT + row[q]) < 0;
-            if constexpr (MODE == 2 && FLTEE_KEYED_SPLIT)
-                return asc ^ ((int32_t)(X + keyed_c(key, (uint32_t)q << dlog)) < 0);
-            if constexpr (MODE == 2 && FLTEE_KEYED_DIRFOLD) return keyed_swap(kb, (uint32_t)q << dlog);
+            if constexpr (MODE == 2) return keyed_swap(kb, (uint32_t)q << dlog);
             return asc ^ cond2<MODE>(v[q], v[qm], p0 + ((uint32_t)q << dlog), key);
         };
-#if FLTEE_CE_BATCH
         // every swap decision of the step first, then the selects: the compares are
         // independent, so their mask chains (v_cmp -> s_xor -> v_cndmask) overlap
         bool sw[(1 << R) / 2];
@@ -315,33 +140,10 @@ __device__ __forceinline__ void group_steps(uint64_t (&v)[1 << R], uint32_t p0, 
             v[q] = s ? c : a;
             v[qm] = s ? a : c;
         }
-#else
-#pragma unroll
-        for (int q = 0; q < (1 << R); ++q) {
-            if (q & (1 << lv)) continue;
-            const int qm = q | (1 << lv);
-            const uint64_t a = v[q], c = v[qm];
-            const bool sw = decide(q, qm);
-            v[q] = sw ? c : a;
-            v[qm] = sw ? a : c;
-        }
-#endif
     }
 }
 
-// An 8-B LDS read the compiler does not pair into ds_read2_b64: on gfx950 that form takes
-// 8 LDS cycles for two 512-B wave accesses, two ds_read_b64 take 4 (MI355X_MICROARCH.md
-// LDS table).  A volatile access is never merged (FLTEE_LDS_READ1).
-__device__ __forceinline__ uint64_t lds_ld(const uint64_t *p) {
-#if FLTEE_LDS_READ1
-    typedef __attribute__((address_space(3))) const volatile uint64_t lds_cv_u64;
-    return *(lds_cv_u64 *)p;
-#else
-    return *p;
-#endif
-}
-
-// The lane id, re-defined where it is read (FLTEE_TID_FRESH): a round's per-lane LDS
+// The lane id, re-defined where it is read: a round's per-lane LDS
 // addresses are then computed in the round (a few VALU) instead of being hoisted out of
 // the tile loop as loop invariants and spilled (a spill's reload waits vmcnt(0), i.e. for
 // the previous tile's stores and the prefetch in flight).
@@ -350,7 +152,7 @@ __device__ __forceinline__ uint64_t lds_ld(const uint64_t *p) {
 template <int NT>
 __device__ __forceinline__ uint32_t lane_tid() {
     uint32_t t = threadIdx.x;
-    if constexpr (FLTEE_TID_FRESH && NT >= 1024) asm volatile("; lane_tid" : "+v"(t));
+    if constexpr (NT >= 1024) asm volatile("; lane_tid" : "+v"(t));
     return t;
 }
 
@@ -425,8 +227,12 @@ __device__ __forceinline__ void tl_store(__amdgpu_buffer_rsrc_t rs, uint32_t vl,
     else bt_store<kTileCP>(rs, vl, u * 8u, v);
 }
 
-// Two adjacent records (16 B, the lane part even): the tile passes' slot pairs.  Stores
-// fenced with s_nop 1 (the dwordx4 store data hazard, see bitonic_merge_direct).
+// Two adjacent records (16 B, the lane part even): the tile passes' slot pairs.
+// 16-B stores: hipcc (ROCm 7.2) may let the next group's VALU overwrite a dwordx4 store's
+// data registers one instruction after the store, before the store has read them (measured:
+// nondeterministic output); the explicit "s_nop 1" fenced by sched_barriers gives the two
+// wait states the hazard needs (cdna_hip_programming.md §5.7: dwordx3/x4 stores end with
+// s_nop 1).
 template <bool SW>
 __device__ __forceinline__ void tl_load2(__amdgpu_buffer_rsrc_t rs, uint32_t vl, uint32_t u, uint64_t &a,
                                          uint64_t &b) {
@@ -493,7 +299,7 @@ __device__ __forceinline__ void lds_round(uint64_t *sm, uint32_t base, uint32_t 
         for (int h = 0; h < BW; ++h) {
             b[h] = spread(lane_tid<NT>() + (uint32_t)(h0 + h) * NT, dlog, R);
 #pragma unroll
-            for (int q = 0; q < (1 << R); ++q) v[h][q] = lds_ld(&sm[lpad(b[h] + ((uint32_t)q << dlog))]);
+            for (int q = 0; q < (1 << R); ++q) v[h][q] = sm[lpad(b[h] + ((uint32_t)q << dlog))];
         }
 #pragma unroll
         for (int h = 0; h < BW; ++h)
@@ -566,10 +372,10 @@ __device__ __forceinline__ void lds_round_ct(uint64_t *sm, uint32_t base, uint32
         if constexpr (DLOG + R >= 4) {
             const uint64_t *row = sm + lpad(b[h]);
 #pragma unroll
-            for (int q = 0; q < (1 << R); ++q) v[h][q] = lds_ld(&row[(q << DLOG) + ((q << DLOG) >> 4)]);
+            for (int q = 0; q < (1 << R); ++q) v[h][q] = row[(q << DLOG) + ((q << DLOG) >> 4)];
         } else {  // a group inside 16 records: the padding slot may fall between its records
 #pragma unroll
-            for (int q = 0; q < (1 << R); ++q) v[h][q] = lds_ld(&sm[lpad(b[h] + ((uint32_t)q << DLOG))]);
+            for (int q = 0; q < (1 << R); ++q) v[h][q] = sm[lpad(b[h] + ((uint32_t)q << DLOG))];
         }
     }
 #pragma unroll
@@ -606,26 +412,25 @@ __device__ __forceinline__ void lds_steps_ct(uint64_t *sm, uint32_t base, uint32
 }
 
 // stages IL..TL-1 in full and stage TL down to step RL (bitonic_sort_direct's LDS part).
-// With FLTEE_WAVE_LOCAL the stages up to log2(64 E) (every step inside the wave's own
+// The stages up to log2(64 E) (every step inside the wave's own
 // records) run as wave-local rounds — no block barrier, so the waves drift apart and one
 // wave's LDS traffic overlaps another's compare-exchanges — and one block barrier
 // precedes the first stage that crosses waves.  The caller orders the LDS writes in front
 // of the first round (a block barrier, or the wave's own order when WAVE_FIRST).
 template <int E>
 constexpr int kWaveLog = E >= 32 ? 11 : (E >= 16 ? 10 : (E >= 8 ? 9 : (E >= 4 ? 8 : 7)));
-// Steps IL-1 .. JBOT of stage IL (> log2(64 E) with FLTEE_WAVE_SPLIT): the steps of
+// Steps IL-1 .. JBOT of stage IL.  Where IL > log2(64 E) and the split adds no LDS round: the steps of
 // distance >= 64 E cross waves and run block-wide; the rest stay inside each wave's 64 E
 // consecutive records and run as wave-local rounds (no block barrier: the waves drift and
 // overlap one another's LDS traffic with their compare-exchanges), then one block barrier.
 // The same steps in the same order: the network is unchanged.  Ends in a block barrier.
 template <int MODE, int E, int NT, int IL, int JBOT>
 __device__ __forceinline__ void stage_steps_ct(uint64_t *sm, uint32_t base, uint32_t seed) {
-    constexpr int WB = FLTEE_WAVE_LOCAL ? kWaveLog<E> : 0;
+    constexpr int WB = kWaveLog<E>;
     constexpr int rmax = E >= 32 ? 5 : (E >= 16 ? 4 : (E >= 8 ? 3 : (E >= 4 ? 2 : 1)));
     constexpr int r_all = (IL - JBOT + rmax - 1) / rmax;
-    constexpr int r_split = WB ? (IL - WB + rmax - 1) / rmax + (WB - JBOT + rmax - 1) / rmax : 0;
-    constexpr bool split = WB != 0 && FLTEE_WAVE_SPLIT != 0 && IL > WB && JBOT < WB &&
-                           (FLTEE_WAVE_SPLIT == 1 || r_split <= r_all);
+    constexpr int r_split = (IL - WB + rmax - 1) / rmax + (WB - JBOT + rmax - 1) / rmax;
+    constexpr bool split = IL > WB && JBOT < WB && r_split <= r_all;
     if constexpr (split) {
         lds_steps_ct<MODE, E, NT, IL - 1, WB>(sm, base, (uint32_t)IL, seed);
         lds_steps_ct<MODE, E, NT, WB - 1, JBOT, 0, WB>(sm, base, (uint32_t)IL, seed);
@@ -637,9 +442,9 @@ __device__ __forceinline__ void stage_steps_ct(uint64_t *sm, uint32_t base, uint
 
 template <int MODE, int E, int NT, int IL, int TL, int RL>
 __device__ __forceinline__ void sort_stages_ct(uint64_t *sm, uint32_t base, uint32_t seed) {
-    constexpr int WB = FLTEE_WAVE_LOCAL ? kWaveLog<E> : 0;
+    constexpr int WB = kWaveLog<E>;
     if constexpr (IL < TL) {
-        if constexpr (WB && IL <= WB) {
+        if constexpr (IL <= WB) {
             lds_steps_ct<MODE, E, NT, IL - 1, 0, 0, WB>(sm, base, (uint32_t)IL, seed);
             if constexpr (IL == WB) __syncthreads();  // the next stage crosses waves
         } else {
@@ -649,7 +454,7 @@ __device__ __forceinline__ void sort_stages_ct(uint64_t *sm, uint32_t base, uint
     } else {
         // stage TL runs block-wide rounds: if the stage before it was wave-local and did
         // not end in a block barrier (TL <= WB), order the waves here
-        if constexpr (WB && TL <= WB) __syncthreads();
+        if constexpr (TL <= WB) __syncthreads();
         stage_steps_ct<MODE, E, NT, TL, RL>(sm, base, seed);
     }
 }
@@ -683,7 +488,7 @@ __global__ __launch_bounds__(NT) void bitonic_tiles(uint64_t *__restrict__ data,
     // P2: lane t holds the slot pairs 2t, 2t + 1 (+ 2 NT r) — adjacent positions (the
     // compile-time shapes have W >= 2; SW keeps bits 0..3), one 16-B load and store each
     // (PR: a run-time shape whose launcher checked wlog >= 1)
-    constexpr bool P2 = FLTEE_TILE_PAIRS && !SORT && (TL != 0 || PR);
+    constexpr bool P2 = !SORT && (TL != 0 || PR);
     constexpr uint32_t LS = P2 ? 2u : 1u;  // records per load
     auto elem = [](int r) -> uint32_t {     // the tile element held in pf[r]
         return P2 ? 2u * threadIdx.x + (uint32_t)(r & 1) + (uint32_t)(r >> 1) * (2u * NT)
@@ -716,7 +521,7 @@ __global__ __launch_bounds__(NT) void bitonic_tiles(uint64_t *__restrict__ data,
     // before they go to LDS (one LDS write + read of the tile less, as in
     // bitonic_merge_direct)
     constexpr int RH = P2 ? R1 - 1 : R1;  // the head round's steps
-    constexpr bool kHeadReg = FLTEE_TILE_HEADREG && TL != 0 && WL != 0 && !SORT && RH >= 1 && (TL - RH) >= WL;
+    constexpr bool kHeadReg = TL != 0 && WL != 0 && !SORT && RH >= 1 && (TL - RH) >= WL;
     for (;;) {
         const uint32_t base = tile_base(past_hole(tile, hole_at, hole_len), tlog, wlog, dtile);
         const bool head_reg = kHeadReg && seg0 == 0;
@@ -741,12 +546,11 @@ __global__ __launch_bounds__(NT) void bitonic_tiles(uint64_t *__restrict__ data,
         for (int r = 0; r < E; ++r) sm[lpad(elem(r))] = pf[r];
         __syncthreads();
         const uint32_t next = tile + gridDim.x;
-        // always prefetch (the last round re-reads its own tile) so no branch wraps the loads
-        // FLTEE_TILE_SKIP_SELF: a block on its last tile prefetches nothing (one uniform
-        // branch around the whole prefetch; else it re-reads its own tile)
+        // a block on its last tile prefetches nothing (one uniform branch around the whole
+        // prefetch, none around a single load)
         auto prefetch = [&]() {
-            if (!FLTEE_TILE_SKIP_SELF || next < ntiles)
-                load_tile(tile_base(past_hole(next < ntiles ? next : tile, hole_at, hole_len), tlog, wlog, dtile));
+            if (next < ntiles)
+                load_tile(tile_base(past_hole(next, hole_at, hole_len), tlog, wlog, dtile));
         };
         // compile-time strided tiles: the prefetch after the fused tail's rounds (its
         // registers are then not live through the tail)
@@ -764,11 +568,7 @@ __global__ __launch_bounds__(NT) void bitonic_tiles(uint64_t *__restrict__ data,
                 // compile-time rounds like the rows below; any other top: runtime rounds
                 const uint32_t st = (seg0 >> 8) & 0xFFFFu;
                 bool done = false;
-                // (2^12 tiles of 512 lanes; the 1024-lane 2^14 tiles are held to 128 VGPRs
-                // and spill with the tail unrolled: C5 14.82 -> 15.44 ms, so they keep
-                // runtime tail rounds, `profiles/r02/ab/tail_ct.jsonl`)
-                if constexpr (TL != 0 && WL != 0 && (MODE != 2 || FLTEE_TAIL_CT_KEYED) &&
-                              (NT <= 512 || FLTEE_TAIL_CT_1024)) {
+                if constexpr (TL != 0 && WL != 0) {
                     if ((seg0 & 0xFFu) == (uint32_t)WL - 1u) {
                         lds_steps_ct<MODE, E, NT, WL - 1, 0, WL>(sm, base + pbase, st, seed, dtile);
                         done = true;
@@ -797,12 +597,12 @@ __global__ __launch_bounds__(NT) void bitonic_tiles(uint64_t *__restrict__ data,
         if constexpr (P2) {
 #pragma unroll
             for (int r = 0; r < E; r += 2)
-                tl_store2<SWO_>(rs, voffo, base + (uint32_t)(r >> 1) * rrow, lds_ld(&sm[lpad(elem(r))]),
-                              lds_ld(&sm[lpad(elem(r + 1))]));
+                tl_store2<SWO_>(rs, voffo, base + (uint32_t)(r >> 1) * rrow, sm[lpad(elem(r))],
+                              sm[lpad(elem(r + 1))]);
         } else {
 #pragma unroll
             for (int r = 0; r < E; ++r)
-                tl_store<SWO_>(rs, voffo, base + (uint32_t)r * rrow, lds_ld(&sm[lpad(threadIdx.x + r * NT)]));
+                tl_store<SWO_>(rs, voffo, base + (uint32_t)r * rrow, sm[lpad(threadIdx.x + r * NT)]);
         }
         if (next >= ntiles) break;
         __syncthreads();  // this tile's LDS reads retire before the next tile lands
@@ -827,6 +627,13 @@ __global__ __launch_bounds__(NT) void bitonic_tiles(uint64_t *__restrict__ data,
 // tile was read into LDS before, so the in-place writes are safe.
 // SWI / SWO: the tile is read / written in the block-swizzled layout (kSwzMask; the
 // contiguous merges only: a middle merge both, the last merge of a sort SWI alone).
+// Since round 4 launch_tiles sends only the selecting pass here (every other contiguous
+// merge runs as a plain tile pass with 16-B slot pairs: C4 8.02 -> 8.00 ms, C5 12.28 ->
+// 12.26 ms, `profiles/r04/ab/ab16_tile_merges_*.jsonl`), so the !SEL, STRIDED and SWO
+// instantiations are never launched.  They stay compiled: taking them out of the code
+// object changes hipcc's register allocation in two other kernels (bitonic_sort_direct<2,
+// 16, 512, 1, GEN, 13>), so they go with the next change that alters those kernels anyway
+// ("A/B builds and their knobs").
 template <int MODE, int E, int NT, int RL, bool STRIDED, bool SEL = false, int TL = 0,
           bool SWI = false, bool SWO = false>
 __global__ __launch_bounds__(NT) void bitonic_merge_direct(uint64_t *__restrict__ data,
@@ -852,7 +659,7 @@ __global__ __launch_bounds__(NT) void bitonic_merge_direct(uint64_t *__restrict_
     // P2 (contiguous, compile-time shape): lane t loads the slot pairs 2t, 2t + 1 (+ 2 NT r),
     // 16 B each; the head round in registers then covers the top R1 - 1 steps per parity
     // class and the last round takes one step more (RL + 1): the same LDS rounds
-    constexpr bool P2 = (FLTEE_MERGE_PAIRS == 1 || (FLTEE_MERGE_PAIRS == 2 && SEL)) && TL != 0 && !STRIDED && RL < R1;
+    constexpr bool P2 = SEL && TL != 0 && !STRIDED && RL < R1;
     constexpr int RH = P2 ? R1 - 1 : R1;  // head round (registers)
     constexpr int RT = P2 ? RL + 1 : RL;  // last round (registers)
     auto elem = [&](int r) -> uint32_t {  // the tile element held in pf[r]
@@ -904,7 +711,7 @@ __global__ __launch_bounds__(NT) void bitonic_merge_direct(uint64_t *__restrict_
             uint64_t v[E];
             const uint64_t *own = sm + lpad(t * (uint32_t)E);  // E >= 16: lpad splits
 #pragma unroll
-            for (int q = 0; q < E; ++q) v[q] = lds_ld(&own[q + (q >> 4)]);
+            for (int q = 0; q < E; ++q) v[q] = own[q + (q >> 4)];
             uint32_t c = 0;
 #pragma unroll
             for (int h = 0; h < G; ++h) {
@@ -931,21 +738,6 @@ __global__ __launch_bounds__(NT) void bitonic_merge_direct(uint64_t *__restrict_
                 pre += w < wv ? x : 0u;
                 tot += x;
             }
-#if FLTEE_SEL_STORE_OOB
-            // branch-free: every record is stored, the unselected ones at the first byte
-            // past the tile's own slot of a tile-sized buffer resource, where the store is
-            // dropped (no data-dependent branch, no per-record exec mask kept live)
-            const uint32_t tbytes = (1u << tlog) * 8u;
-            const __amdgpu_buffer_rsrc_t ts =
-                __builtin_amdgcn_make_buffer_rsrc((void *)(data + base), (short)0, (int)tbytes, 0x00020000);
-            uint32_t o = pre + inc - c;  // tile-relative
-#pragma unroll
-            for (int q = 0; q < E; ++q) {
-                const bool sq = (uint32_t)v[q] < sel_d;
-                bt_store<kTileCP>(ts, sq ? o * 8u : tbytes, 0u, v[q]);
-                o += sq ? 1u : 0u;
-            }
-#else
             uint32_t o = base + pre + inc - c;
 #pragma unroll
             for (int q = 0; q < E; ++q) {
@@ -954,7 +746,6 @@ __global__ __launch_bounds__(NT) void bitonic_merge_direct(uint64_t *__restrict_
                     ++o;
                 }
             }
-#endif
             if (t == NT - 1) sel_cnt[ptile] = tot;
             if (next >= ntiles) break;
             __syncthreads();  // wtot and the last round's LDS reads retire
@@ -977,10 +768,10 @@ __global__ __launch_bounds__(NT) void bitonic_merge_direct(uint64_t *__restrict_
             if (!STRIDED) {  // b = g << RT: lpad(b + q) = lpad(b) + q + (q >> 4)
                 const uint64_t *row = sm + lpad(b);
 #pragma unroll
-                for (int q = 0; q < (1 << RT); ++q) vv[h][q] = lds_ld(&row[q + (q >> 4)]);
+                for (int q = 0; q < (1 << RT); ++q) vv[h][q] = row[q + (q >> 4)];
             } else {
 #pragma unroll
-                for (int q = 0; q < (1 << RT); ++q) vv[h][q] = lds_ld(&sm[lpad(b + ((uint32_t)q << jbot))]);
+                for (int q = 0; q < (1 << RT); ++q) vv[h][q] = sm[lpad(b + ((uint32_t)q << jbot))];
             }
         }
 #pragma unroll
@@ -1030,21 +821,18 @@ __global__ __launch_bounds__(NT) void bitonic_merge_direct(uint64_t *__restrict_
 template <int MODE, int IL, int E>
 __device__ __forceinline__ void lane_stage(uint64_t (&v)[E], uint32_t p0, uint32_t seed) {
     constexpr int B = 1 << IL;
-    if constexpr (MODE == 2 && FLTEE_KEY_AFTER_DATA) seed = after_data(seed, (uint32_t)v[0]);
+    if constexpr (MODE == 2) seed = after_data(seed, (uint32_t)v[0]);
 #pragma unroll
     for (int lv = IL - 1; lv >= 0; --lv) {
         const uint32_t key = MODE == 2 ? shuffle_step_key(seed, IL, (uint32_t)lv) : 0u;
-        // p0 is a multiple of E: l = p0 + q = p0 ^ q (keyed_c)
-        const uint32_t X = (MODE == 2 && FLTEE_KEYED_SPLIT) ? (p0 ^ key) * 0x9E3779B1u : 0u;
+        // p0 is a multiple of E: l = p0 + q = p0 ^ q (keyed_swap)
         bool sw[E / 2];
 #pragma unroll
         for (int q = 0, k = 0; q < E; ++q) {
             if (q & (1 << lv)) continue;
             const int qm = q | (1 << lv);
             const bool asc = ((p0 + (uint32_t)(q & ~(B - 1))) & (1u << IL)) == 0;
-            if constexpr (MODE == 2 && FLTEE_KEYED_SPLIT)
-                sw[k++] = asc ^ ((int32_t)(X + keyed_c(key, (uint32_t)q)) < 0);
-            else if constexpr (MODE == 2 && FLTEE_KEYED_DIRFOLD)
+            if constexpr (MODE == 2)
                 sw[k++] = keyed_swap(p0 ^ key ^ keyed_dir(asc), (uint32_t)q);
             else
                 sw[k++] = asc ^ cond2<MODE>(v[q], v[qm], p0 + (uint32_t)q, key);
@@ -1093,10 +881,10 @@ __device__ __forceinline__ uint64_t gen_entry(const SortGen &g, uint32_t p, uint
 // last work in registers: lane t loads records tE .. tE+E-1 (16-B loads), runs stages
 // 1..log2 E on them without LDS, and writes them to LDS; the LDS rounds run stages
 // log2 E + 1 .. tlog; the last round of stage tlog (groups of 2^RL consecutive records)
-// stores straight to HBM (16-B stores fenced with s_nop 1, see bitonic_merge_direct).
+// stores straight to HBM (16-B stores fenced with s_nop 1, see tl_store2).
 // SWO: the sorted tiles are written in the block-swizzled layout (kSwzMask; the loads
 // are logical), for a sort whose later passes run swizzled.
-template <int MODE, int E, int NT, int RL, int GEN = 0, int TL = 0, int LPF = 1, bool SWO = false>
+template <int MODE, int E, int NT, int RL, int GEN = 0, int TL = 0, bool SWO = false>
 __global__ __launch_bounds__(NT) void bitonic_sort_direct(uint64_t *__restrict__ data,
                                                           uint32_t tlog, uint32_t seed,
                                                           uint32_t ntiles, uint32_t pbase,
@@ -1212,35 +1000,16 @@ __global__ __launch_bounds__(NT) void bitonic_sort_direct(uint64_t *__restrict__
 #pragma unroll
         for (int r = 0; r < E; ++r) sm[lpad(t * (uint32_t)E + (uint32_t)r)] = pf[r];
         // the lane's records are positions tE .. tE + E - 1: the wave's own 64 E records,
-        // which its wave-local first rounds read back (TL != 0 with FLTEE_WAVE_LOCAL)
-        if constexpr (TL != 0 && FLTEE_WAVE_LOCAL && R1 + 1 <= kWaveLog<E>) wave_lds_order();
+        // which its wave-local first rounds read back (TL != 0)
+        if constexpr (TL != 0 && R1 + 1 <= kWaveLog<E>) wave_lds_order();
         else __syncthreads();
         const uint32_t next = tile + stride;
         if constexpr (TL != 0) {  // tlog == TL (launcher)
-            // the next tile's loads go out before the LAST stage's rounds, not before the
-            // first: the prefetch registers stay free through the rounds of stages
-            // log2 E + 1 .. TL - 1 (1024 lanes are held to 128 VGPRs; with the prefetch
-            // live across every round the 2^14-tile kernels spilled), and stage TL's
-            // rounds still cover the load latency (LPF 0: before the first round)
-            // LPF 2: later still, before stage TL's last LDS round.  That round is forced to
-            // a full R1-step round (steps kLast .. RL, kLast = RL + R1 - 1) and the steps
-            // above it are regrouped greedily; this is not always lds_steps_ct's own greedy
-            // split (whenever (TL - RL) % R1 != 0), but the steps still run one after the
-            // other in the same order, so the network and its output are unchanged.
-            constexpr int kLast = RL + R1 - 1;
-            if constexpr (LPF == 2 && kLast < TL - 1) {
-                sort_stages_ct<MODE, E, NT, R1 + 1, TL - 1, 0>(sm, base + pbase, seed);
-                lds_steps_ct<MODE, E, NT, TL - 1, kLast + 1>(sm, base + pbase, (uint32_t)TL, seed);
-                issue(next < ntiles ? next : tile);
-                lds_steps_ct<MODE, E, NT, kLast, RL>(sm, base + pbase, (uint32_t)TL, seed);
-            } else if constexpr (LPF != 0) {
-                sort_stages_ct<MODE, E, NT, R1 + 1, TL - 1, 0>(sm, base + pbase, seed);
-                issue(next < ntiles ? next : tile);
-                lds_steps_ct<MODE, E, NT, TL - 1, RL>(sm, base + pbase, (uint32_t)TL, seed);
-            } else {
-                issue(next < ntiles ? next : tile);
-                sort_stages_ct<MODE, E, NT, R1 + 1, TL, RL>(sm, base + pbase, seed);
-            }
+            // the next tile's loads go out before the first LDS round (before the last stage's
+            // rounds, or its last round, was kept while the kernels spilled: C5 13.69 vs 13.77
+            // ms, C4 9.34 vs 9.35 ms without spills, `profiles/r03/ab/ab4_*.jsonl`)
+            issue(next < ntiles ? next : tile);
+            sort_stages_ct<MODE, E, NT, R1 + 1, TL, RL>(sm, base + pbase, seed);
         } else {
             issue(next < ntiles ? next : tile);
             for (uint32_t il = (uint32_t)R1 + 1; il < tlog; ++il)
@@ -1251,7 +1020,9 @@ __global__ __launch_bounds__(NT) void bitonic_sort_direct(uint64_t *__restrict__
         // every group read from LDS first, then computed, then stored (the fenced stores
         // would otherwise hold the next group's reads behind them)
         constexpr int BW = kLdsBatch<G>;
-        const uint32_t sxb = SWO ? swz_x(base) : 0u;  // the tile's block swizzle (merge_direct)
+        // SWO: a contiguous tile stays in its own 2^14 block, so its records' physical
+        // offsets inside the block are (tile offset ^ swz_x(base)): one uniform XOR
+        const uint32_t sxb = SWO ? swz_x(base) : 0u;
 #pragma unroll
         for (int h0 = 0; h0 < G; h0 += BW) {
         uint64_t vv[BW][1 << RL];
@@ -1260,7 +1031,7 @@ __global__ __launch_bounds__(NT) void bitonic_sort_direct(uint64_t *__restrict__
         for (int h = 0; h < BW; ++h) {
             const uint32_t b = (tf + (uint32_t)(h0 + h) * NT) << RL;
 #pragma unroll
-            for (int q = 0; q < (1 << RL); ++q) vv[h][q] = lds_ld(&sm[lpad(b + (uint32_t)q)]);
+            for (int q = 0; q < (1 << RL); ++q) vv[h][q] = sm[lpad(b + (uint32_t)q)];
         }
 #pragma unroll
         for (int h = 0; h < BW; ++h)
@@ -1369,34 +1140,15 @@ constexpr uint32_t kMaxTileLog = 14;  // 16384 records = 128 KB (+1/16 padding) 
 // Steps per register-blocked global pass: 6 (64 records / lane; fastest at M = 2^24, 2^27).
 constexpr int kRegMaxSteps = 6;
 // Smaller tiles until there are at least 2^8 of them (one per CU).
-#ifndef FLTEE_MIN_TILES_LOG
-#define FLTEE_MIN_TILES_LOG 8
-#endif
-constexpr uint32_t kMinTilesLog = FLTEE_MIN_TILES_LOG;
-// ... but no tile under 2^FLTEE_TILE_FLOOR records for that: below 2^20 records fewer,
+constexpr uint32_t kMinTilesLog = 8;
+// ... but no tile under 2^kTileFloor records for that: below 2^20 records fewer,
 // larger tiles win on launch count (round 5, `profiles/r05/ab/ab7_tile_floor_*.jsonl`,
 // floors 11 / 12 / 13: 2^16 records 0.071 / 0.062 / 0.076 ms, 2^18 0.107 / 0.087 / 0.115;
 // 2^14 tiles were slower at every size)
-#ifndef FLTEE_TILE_FLOOR
-#define FLTEE_TILE_FLOOR 12
-#endif
+constexpr uint32_t kTileFloor = 12;
 // Narrowest strided-tile row, log2: 16 records = 128-B row segments (W = 8: 14.09 vs
 // 14.03 ms at 2^27, W = 4: 14.66, W = 2: 16.37).
 constexpr int kMinWLog = 4;
-// The first pass's prefetch of the next tile: 0 = before the first LDS round, 1 = before
-// the last stage's rounds, 2 = before that stage's last round.  Round 2 kept it late (2
-// for the sorts by key, 1 for the keyed shuffle) because the kernels spilled; without
-// spills (lane_tid, the producer moved out of the prefetch) the earliest is fastest: C5
-// 13.69 vs 13.77 ms (2), C4 9.34 vs 9.35 ms (1) (`profiles/r03/ab/ab4_*.jsonl`).
-// Overridable at build time for A/B libraries only (scripts/ab_build.sh).
-#ifndef FLTEE_SORT_LATEPF_KEY
-#define FLTEE_SORT_LATEPF_KEY 0
-#endif
-#ifndef FLTEE_SORT_LATEPF_SHUFFLE
-#define FLTEE_SORT_LATEPF_SHUFFLE 0
-#endif
-template <int MODE>
-constexpr int kSortLatePf = MODE == 2 ? FLTEE_SORT_LATEPF_SHUFFLE : FLTEE_SORT_LATEPF_KEY;
 
 template <int MODE, bool SORT, int E, int NT, int TL, int WL, bool LPF, bool SW, bool PR = false>
 static hipError_t launch_tiles_pr(unsigned grid, size_t lds, hipStream_t s, uint64_t *data,
@@ -1415,15 +1167,12 @@ static hipError_t launch_tiles_pr(unsigned grid, size_t lds, hipStream_t s, uint
     return hipGetLastError();
 }
 // the run-time-shaped 2^14 tiles take the slot pairs too when their rows have >= 2 records
-#ifndef FLTEE_TILE_PAIRS_RT
-#define FLTEE_TILE_PAIRS_RT 1
-#endif
 template <int MODE, bool SORT, int E, int NT, int TL, int WL, bool LPF, bool SW>
 static hipError_t launch_tiles_sw(unsigned grid, size_t lds, hipStream_t s, uint64_t *data,
                                   uint32_t tlog, uint32_t ilog, uint32_t wlog, uint32_t dtile,
                                   uint32_t seed, uint32_t tiles, uint32_t pbase, uint32_t seg0,
                                   uint32_t hole_at, uint32_t hole_len) {
-    if constexpr (FLTEE_TILE_PAIRS_RT && TL == 0 && !SORT && NT == 1024 && E == 16) {
+    if constexpr (TL == 0 && !SORT && NT == 1024 && E == 16) {
         if (wlog >= 1)
             return launch_tiles_pr<MODE, SORT, E, NT, TL, WL, LPF, SW, true>(grid, lds, s, data, tlog, ilog, wlog,
                                                                             dtile, seed, tiles, pbase, seg0,
@@ -1488,6 +1237,7 @@ struct SelSink {
     uint32_t *cnt = nullptr;  // null: no sink
 };
 
+// (launch_tiles calls it for the selecting last pass only: see bitonic_merge_direct)
 template <int MODE, int E, int NT, bool STRIDED>
 static hipError_t launch_direct(const TileCfg &c, hipStream_t s, uint64_t *data, uint32_t ilog,
                                 uint32_t wlog, uint32_t dtile, uint32_t seed, uint32_t pbase,
@@ -1572,23 +1322,22 @@ static hipError_t launch_sort_direct(const TileCfg &c, hipStream_t s, uint64_t *
         bytes += (uint64_t)8 * gg.pad_n;  // ... + the pad tiles' stores
     }
     net_account(bytes, "bitonic_sort_direct", s);
-#define BS_GO_SW(RL_, TL_, LPF_, SWO_)                                                             \
+#define BS_GO_SW(RL_, TL_, SWO_)                                                                   \
     do {                                                                                           \
         static bool attr = false;                                                                  \
         if (!attr) {                                                                               \
-            (void)hipFuncSetAttribute((const void *)bitonic_sort_direct<MODE, E, NT, RL_, GEN, TL_, LPF_, SWO_>, \
+            (void)hipFuncSetAttribute((const void *)bitonic_sort_direct<MODE, E, NT, RL_, GEN, TL_, SWO_>, \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
             attr = true;                                                                           \
         }                                                                                          \
-        FLTEE_LAUNCH((bitonic_sort_direct<MODE, E, NT, RL_, GEN, TL_, LPF_, SWO_>), dim3(grid), \
+        FLTEE_LAUNCH((bitonic_sort_direct<MODE, E, NT, RL_, GEN, TL_, SWO_>), dim3(grid), \
                            dim3(NT), c.lds, s, data, c.tlog, seed, c.tiles, pbase, gg);            \
     } while (0)
-#define BS_GO_PF(RL_, TL_, LPF_) BS_GO_SW(RL_, TL_, LPF_, false)
-#define BS_GO(RL_, TL_) BS_GO_PF(RL_, TL_, ((TL_) != 0 ? kSortLatePf<MODE> : 1))
+#define BS_GO(RL_, TL_) BS_GO_SW(RL_, TL_, false)
     // the usual tile sizes: every stage's LDS rounds unrolled at compile time
     if constexpr (E == 16 && NT == 1024) {
         if (c.tlog == 14 && rl == 2) {
-            if (swo) BS_GO_SW(2, 14, kSortLatePf<MODE>, true);
+            if (swo) BS_GO_SW(2, 14, true);
             else BS_GO(2, 14);
             return hipGetLastError();
         }
@@ -1608,7 +1357,6 @@ static hipError_t launch_sort_direct(const TileCfg &c, hipStream_t s, uint64_t *
     default: if constexpr (R1 >= 5) BS_GO(5, 0); break;
     }
 #undef BS_GO
-#undef BS_GO_PF
 #undef BS_GO_SW
     return hipGetLastError();
 }
@@ -1628,18 +1376,10 @@ static hipError_t launch_tiles(const TileCfg &c, hipStream_t s, uint64_t *data, 
         if (c.NT == 512 && c.E == 16) return launch_sort_direct<MODE, 16, 512>(c, s, data, seed, pbase);
         if (c.NT == 512 && c.E == 8) return launch_sort_direct<MODE, 8, 512>(c, s, data, seed, pbase);
     }
-    // contiguous merges of 2^13 / 2^14 tiles: first and last round in registers
-    // (A/B at 2^27: 13.89 vs 14.63 ms mode 0, 14.55 vs 15.65 ms mode 2; 2^24: -6 %)
-    // FLTEE_DIRECT_MERGE 0 (round 4): a merge that neither selects nor changes layout runs as
-    // a plain contiguous tile pass with 16-B slot pairs instead of the direct merge (8-B
-    // loads for its register head round): C4 8.02 -> 8.00 ms, C5 12.28 -> 12.26 ms
-    // (`profiles/r04/ab/ab16_tile_merges_*.jsonl`); the selecting last pass and the last
-    // merge of a swizzled sort (reads swizzled, writes in order) stay direct
-    const bool direct = FLTEE_DIRECT_MERGE || sink.cnt || (sw.in != sw.out && !FLTEE_UNSW_TILES);
     if constexpr (!SORT) {
         // the last merge of a swizzled sort as a slot-pair tile pass that reads swizzled and
-        // writes in order (FLTEE_UNSW_TILES)
-        if (!direct && sw.in && !sw.out && plain && wlog == c.tlog && c.NT == 1024 && c.E == 16 &&
+        // writes in order
+        if (!sink.cnt && sw.in && !sw.out && plain && wlog == c.tlog && c.NT == 1024 && c.E == 16 &&
             c.tlog == 14) {
             static bool attr = false;
             if (!attr) {
@@ -1655,11 +1395,14 @@ static hipError_t launch_tiles(const TileCfg &c, hipStream_t s, uint64_t *data, 
             return hipGetLastError();
         }
     }
-    if (!SORT && plain && wlog == c.tlog && c.tlog > 6 && direct) {
+    // the selecting last pass of 2^13 / 2^14 tiles: the direct merge, first and last round in
+    // registers.  (Every other contiguous merge runs as a plain tile pass with 16-B slot
+    // pairs: C4 8.02 -> 8.00 ms, C5 12.28 -> 12.26 ms, `profiles/r04/ab/ab16_tile_merges_*.jsonl`.)
+    if (!SORT && plain && wlog == c.tlog && c.tlog > 6 && sink.cnt) {
         if (c.NT == 1024) return launch_direct<MODE, 16, 1024, false>(c, s, data, ilog, wlog, dtile, seed, pbase, sink, sw);
         if (c.NT == 512 && c.E == 16 && !sw.in && !sw.out)
             return launch_direct<MODE, 16, 512, false>(c, s, data, ilog, wlog, dtile, seed, pbase, sink);
-    }  // (E <= 8 tiles, M <= 2^20: measured no faster, 175 vs 169 us at 2^20)
+    }
     if (sink.cnt) return hipErrorNotSupported;  // only the direct contiguous merge selects
     // the other tile passes are in place: a swizzled one reads and writes that layout
     if (sw.in != sw.out || (sw.in && (SORT || c.NT != 1024 || c.E != 16))) return hipErrorInvalidValue;
@@ -1667,32 +1410,22 @@ static hipError_t launch_tiles(const TileCfg &c, hipStream_t s, uint64_t *data, 
     // 14.03 ms at 2^27, the last round's 8-B stores land 2^dtile apart)
     // strided passes of the usual tile sizes, rows of 2^4 .. 2^7 (and, for 2^12 tiles, the
     // planned tiles' 2^8 .. 2^9, whose tails fill the consecutive bits): compile-time rounds
-    const uint32_t wmin = c.NT == 1024 ? (uint32_t)FLTEE_TILE_MINW14 : (uint32_t)FLTEE_TILE_MINW12;
-    if (!SORT && ilog != 0 && wlog < c.tlog && wlog >= wmin && (1u << wlog) <= c.NT &&
+    if (!SORT && ilog != 0 && wlog < c.tlog && wlog >= (uint32_t)kMinWLog && (1u << wlog) <= c.NT &&
         ((c.NT == 1024 && c.E == 16 && c.tlog == 14) || (c.NT == 512 && c.E == 8 && c.tlog == 12)) &&
-        (wlog <= 7 || (seg0 && MODE != 2 && c.NT <= 512) || (FLTEE_TILE_W10 && c.NT == 1024 && wlog == 10) ||
-         (FLTEE_TILE_MINW14 < 4 && c.NT == 1024 && wlog == 8))) {
+        (wlog <= 7 || (seg0 && MODE != 2 && c.NT <= 512) || (c.NT == 1024 && wlog == 10))) {
 #define BT_ST_CASE(E_, NT_, TL_, W_)                                                               \
     case W_: return launch_tiles_e<MODE, SORT, E_, NT_, TL_, W_>(c.grid, c.lds, s, data, c.tlog, ilog, wlog, dtile, seed, c.tiles, pbase, seg0, sw.in, c.hole_at, c.hole_len);
         if (c.NT == 1024) {
             switch (wlog) {
                 BT_ST_CASE(16, 1024, 14, 4) BT_ST_CASE(16, 1024, 14, 5) BT_ST_CASE(16, 1024, 14, 6)
                 BT_ST_CASE(16, 1024, 14, 7)
-#if FLTEE_TILE_MINW14 < 4
-                BT_ST_CASE(16, 1024, 14, 3) BT_ST_CASE(16, 1024, 14, 8)
-#endif
-#if FLTEE_TILE_W10
                 BT_ST_CASE(16, 1024, 14, 10)  // rows of 2^10 (the planned tails on 10 low bits)
-#endif
             default: break;
             }
         } else {
             switch (wlog) {
                 BT_ST_CASE(8, 512, 12, 4) BT_ST_CASE(8, 512, 12, 5) BT_ST_CASE(8, 512, 12, 6)
                 BT_ST_CASE(8, 512, 12, 7)
-#if FLTEE_TILE_MINW12 < 4
-                BT_ST_CASE(8, 512, 12, 3)
-#endif
             default: break;
             }
             if constexpr (MODE != 2) {  // planned tiles only (the keyed shuffle runs per stage)
@@ -1706,7 +1439,7 @@ static hipError_t launch_tiles(const TileCfg &c, hipStream_t s, uint64_t *data, 
     }
 #define BT_GO(E_, NT_) \
     return launch_tiles_e<MODE, SORT, E_, NT_>(c.grid, c.lds, s, data, c.tlog, ilog, wlog, dtile, seed, c.tiles, pbase, seg0, sw.in, c.hole_at, c.hole_len)
-    if (!FLTEE_DIRECT_MERGE && !SORT && plain && wlog == c.tlog && c.NT == 1024 && c.E == 16 && c.tlog == 14)
+    if (!SORT && plain && wlog == c.tlog && c.NT == 1024 && c.E == 16 && c.tlog == 14)
         return launch_tiles_e<MODE, SORT, 16, 1024, 14>(c.grid, c.lds, s, data, c.tlog, ilog, wlog, dtile, seed,
                                                         c.tiles, pbase, 0u, sw.in, c.hole_at, c.hole_len);
     if (c.NT == 1024) BT_GO(16, 1024);
@@ -1737,7 +1470,7 @@ static TileCfg make_cfg(uint32_t mlog, uint32_t slog) {
     if (tlog > slog) tlog = slog;
     const uint32_t mt = kMinTilesLog;
     if (tlog == 14 && mlog - tlog < mt) tlog = 13;
-    while (tlog > FLTEE_TILE_FLOOR && tlog <= 13 && (mlog - tlog) < mt) --tlog;  // >= 2^mt tiles
+    while (tlog > kTileFloor && tlog <= 13 && (mlog - tlog) < mt) --tlog;  // >= 2^mt tiles
     c.tlog = tlog;
     if (tlog <= 6) return c;
     const uint32_t T = 1u << tlog;
@@ -1929,16 +1662,9 @@ struct NetPass {
 };
 
 static std::vector<NetPass> plan_network(uint32_t mlog, uint32_t tlog, uint32_t NT, int rmax) {
-    const bool t14 = tlog == 14 && NT == 1024, t12 = tlog == 12 && NT == 512;
-    const uint32_t minw = t14 ? (uint32_t)FLTEE_TILE_MINW14
-                              : t12 ? (uint32_t)FLTEE_TILE_MINW12 : (uint32_t)kMinWLog;
+    const uint32_t minw = (uint32_t)kMinWLog;
     uint32_t ntl = 0;
     while ((1u << (ntl + 1)) <= NT) ++ntl;  // log2 NT: W <= NT for strided tiles
-    // narrower rows than 2^4: only the row widths launch_tiles has compile-time rounds for
-    auto w_ok = [&](uint32_t w) {
-        if (minw >= 4) return true;
-        return t14 ? ((w >= 3 && w <= 8) || (FLTEE_TILE_W10 && w == 10)) : (w >= 3 && w <= 9);
-    };
     // relative launch costs (MI355X rocprof, `profiles/r02/`): register passes R <= 4 one
     // unit (2^27: 268-280 us, 2^20: 4.5-5.2 us), R = 5 / 6 at 2^27 1.19 / 1.43; strided and
     // two-segment tiles 1.5 (2^27: 404 us) / 1.45 (2^20: 7.3 us); the direct contiguous merge
@@ -1996,7 +1722,7 @@ static std::vector<NetPass> plan_network(uint32_t mlog, uint32_t tlog, uint32_t 
         // middle of stage s (strided tile, low bits idle): steps b .. lo on the row bits
         for (uint32_t rows = 1; rows <= b && rows < tlog; ++rows) {
             const uint32_t lo = b - rows + 1, w = tlog - rows;
-            if (w < minw || w > ntl || lo < w || !w_ok(w)) continue;
+            if (w < minw || w > ntl || lo < w) continue;
             if (last_stage && lo < tlog) continue;
             NetPass p;
             p.ilogB = s; p.wlog = w; p.dtile = lo; p.stage = s;
@@ -2006,7 +1732,7 @@ static std::vector<NetPass> plan_network(uint32_t mlog, uint32_t tlog, uint32_t 
         if (s < mlog) {
             for (uint32_t rows = 1; rows < tlog; ++rows) {
                 const uint32_t w = tlog - rows;
-                if (w < b + 1 || w < minw || w > ntl || !w_ok(w)) continue;
+                if (w < b + 1 || w < minw || w > ntl) continue;
                 if (rows > s) break;
                 const uint32_t lo = s - rows + 1;
                 if (lo < w) continue;
@@ -2062,8 +1788,8 @@ size_t debug_plan(uint32_t mlog, uint32_t tlog, uint32_t NT, int rmax, uint32_t 
 // the planned schedule of a full sort (empty: none, the per-stage one runs)
 template <int MODE>
 static const std::vector<NetPass> *plan_for(uint32_t mlog, const TileCfg &c0) {
-    // (the keyed shuffle planned too since round 3: FLTEE_PLAN_SHUFFLE, `profiles/r03/ab`)
-    if ((MODE == 2 && !FLTEE_PLAN_SHUFFLE) || c0.tlog <= 6 || mlog <= c0.tlog) return nullptr;
+    // (the keyed shuffle planned too since round 3, `profiles/r03/ab`)
+    if (c0.tlog <= 6 || mlog <= c0.tlog) return nullptr;
     const int rcap = (int)mlog - 16 < 4 ? 4 : (int)mlog - 16;
     const int rmax = kRegMaxSteps < rcap ? kRegMaxSteps : rcap;
     const std::vector<NetPass> &plan = cached_plan(mlog, c0.tlog, c0.NT, rmax);
@@ -2137,10 +1863,6 @@ static hipError_t sort_impl(uint64_t *data, size_t m, uint32_t seed, hipStream_t
     const TileCfg c = make_cfg(mlog, slog);
     if (!g_pad_skip) valid = 0;
     hipError_t e;
-    if constexpr (MODE == 2) {
-        e = keyed_table_prepare(seed, s);
-        if (e != hipSuccess) return e;
-    }
     if (c.tlog <= 6) {  // tiles of <= 64 records: every stage is one register pass
         for (uint32_t ilog = 1; ilog <= slog; ++ilog) {
             e = launch_global<MODE>(data, mlog, ilog, ilog - 1, (int)ilog, seed, s, pbase,
@@ -2170,10 +1892,6 @@ static hipError_t merge_impl(uint64_t *data, size_t m, uint32_t seed, hipStream_
                              uint32_t ilog, uint32_t pbase) {
     const uint32_t mlog = log2_pow2(m);
     if (mlog == 0) return hipSuccess;
-    if constexpr (MODE == 2) {
-        const hipError_t e = keyed_table_prepare(seed, s);
-        if (e != hipSuccess) return e;
-    }
     const TileCfg c = make_cfg(mlog, mlog);
     if (c.tlog <= 6)
         return launch_global<MODE>(data, mlog, ilog, mlog - 1, (int)mlog, seed, s, pbase);
@@ -2258,10 +1976,6 @@ static hipError_t sort_gen_impl(uint64_t *data, size_t m, uint32_t seed, const S
     const TileCfg c0 = make_cfg(mlog, mlog);
     if (c0.tlog <= 6) return hipErrorNotSupported;
     if (sink.cnt && !last_pass_is_direct_merge(m)) return hipErrorNotSupported;
-    if constexpr (MODE == 2) {
-        const hipError_t e = keyed_table_prepare(seed, s);
-        if (e != hipSuccess) return e;
-    }
     // the padded array's records (advanced: records ++ initial entries; nips19: records ++
     // dummies); past them only (u32::MAX, +0.0) pads
     const uint64_t nvalid = (uint64_t)g.nrec + (GEN == 1 ? (uint64_t)g.d : (uint64_t)g.d * g.tf);
@@ -2357,10 +2071,6 @@ hipError_t bitonic_steps_range(uint64_t *data, size_t m, uint32_t mode, uint32_t
     if (m > ((size_t)1 << 29)) return hipErrorInvalidValue;
     const uint32_t mlog = log2_pow2(m);
     if (jtop >= mlog || jbot > jtop || jtop >= ilog) return hipErrorInvalidValue;
-    if (mode == 2) {
-        const hipError_t e = keyed_table_prepare(seed, s);
-        if (e != hipSuccess) return e;
-    }
     const int kMaxGlobalR = kRegMaxSteps;
     int top = (int)jtop;
     while (top >= (int)jbot) {

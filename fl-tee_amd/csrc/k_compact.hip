@@ -32,51 +32,23 @@
 
 namespace fltee {
 
-// FLTEE_CP_PICK: 1 = compares + selects; 2 = the staying value as bit operations; 3 = bit
-// operations only, no compare; 4 (default, round 5) = form 3 with a dummy's val left as it
-// was (see cp_pick, cp_out)
-// FLTEE_CP_TWO: two levels per LDS round (3 picks, 4 reads and 1 write per slot) or one
-// (1 pick, 2 reads, 1 write and one more barrier per level).  Round 5 A/B, bit-identical:
-// one level per round is slower though it issues a third fewer picks — C5 12.22 -> 12.26
-// ms, C3 0.1317 -> 0.1350 ms (`profiles/r05/ab/ab16_compact_one_level_rounds_rejected.jsonl`)
-#ifndef FLTEE_CP_TWO
-#define FLTEE_CP_TWO 1
-#endif
-// FLTEE_CP_NOHALO: a residue group's only band loads and keeps no halo rows (they lie past
-// L), so its rows may be twice as wide (compact_pass NH).  Round 5 A/B, bit-identical
-// (`profiles/r05/ab/ab18_*`): C5's last two passes (one band each) ~65 us faster, C5 12.11
-// -> 12.06 ms; C3 unchanged (its last pass is the output-prefix tail).
-#ifndef FLTEE_CP_NOHALO
-#define FLTEE_CP_NOHALO 1
-#endif
-// FLTEE_CP_SKIP_SELF: a block on its last tile prefetches nothing (else it re-reads its own
-// tile, a load with no branch around it).  Round 5 A/B, bit-identical (`ab20_*`): C3 0.1315
-// -> 0.1297 ms (its tail pass, one tile per block, 16.6 -> 14.5 us), C5 unchanged.
-#ifndef FLTEE_CP_SKIP_SELF
-#define FLTEE_CP_SKIP_SELF 1
-#endif
-// FLTEE_CP_PAD_BAND: a one-band pass on rows of 16 padded to the full tile (compact_levels).
-// Round 5 A/B, bit-identical (`profiles/r05/ab/ab19_*`): C5 12.03 -> 12.00 ms (its levels
-// 19-23 on the compile-time levels); dropping that band's halo instead (compact_pass NH)
-// was slower there (488 vs 459 us: a select per level read in a VALU-bound pass), so NH is
-// kept for the bands whose rows it widens (C5's last pass: 293 -> 197 us).
-#ifndef FLTEE_CP_PAD_BAND
-#define FLTEE_CP_PAD_BAND 1
-#endif
-// FLTEE_CP_CT: the compaction passes of the common tile shapes (C5's first and middle passes,
-// the fused kernel's nine levels) with their levels at compile time (cp_levels_ct).  Round 5
-// A/B, bit-identical (`profiles/r05/ab/ab17_*`): C5 12.25 -> 12.15 ms (compact_pass 423 ->
-// 403 us on average); the fused kernel 12.3 -> 11.7 us at MLP-MNIST n = 30, 10.2 -> 9.5 us
-// at n = 3, 19.8 -> 19.7 us at C3.
-#ifndef FLTEE_CP_CT
-#define FLTEE_CP_CT 1
-#endif
-#ifndef FLTEE_CP_PICK
-#define FLTEE_CP_PICK 4
-#endif
+// Variants measured in round 5 and settled, all bit-identical (the losing arms left the
+// source, DESIGN.md names the last tree that carries them):
+//   one level per LDS round instead of two: C5 12.22 -> 12.26 ms, rejected
+//     (`profiles/r05/ab/ab16_compact_one_level_rounds_rejected.jsonl`)
+//   a residue group's only band loads and keeps no halo rows (compact_pass NH): C5 12.11
+//     -> 12.06 ms (kept; `profiles/r05/ab/ab18_*`)
+//   a block on its last tile prefetches nothing: C3 0.1315 -> 0.1297 ms (kept; `ab20_*`)
+//   a one-band pass on rows of 16 padded to the full tile (compact_levels): C5 12.03 ->
+//     12.00 ms (kept; `profiles/r05/ab/ab19_*`)
+//   the common tile shapes' levels at compile time (cp_levels_ct): C5 12.25 -> 12.15 ms
+//     (kept; `profiles/r05/ab/ab17_*`)
+//   the pick as compares + selects, or bit operations that also clear a leaving record's
+//     val: compact_pass 431 vs 420 us at C5, rejected (`profiles/r05/ab/ab10_*`, `ab15_*`)
+
 // an unselected slot in flight: c = 2^31 (bit j clear at every level j <= 28, so it never
-// moves; form 1's u32::MAX carried the same meaning through its top-bit test), +0.0
-constexpr uint64_t CP_DUMMY = FLTEE_CP_PICK >= 3 ? 0x80000000ull : 0xFFFFFFFFull;
+// moves), +0.0
+constexpr uint64_t CP_DUMMY = 0x80000000ull;
 constexpr uint64_t CP_PAD = 0xFFFFFFFFull;  // a pad record (idx u32::MAX, +0.0) outside the array
 
 // In flight the key is not idx but c = p0 - idx, the record's total left shift
@@ -84,71 +56,34 @@ constexpr uint64_t CP_PAD = 0xFFFFFFFFull;  // a pad record (idx u32::MAX, +0.0)
 // (idx >= d).  Level j moves a record iff bit j of c is set (c < 2^29; a dummy never
 // moves, and a slot it occupies stays a dummy).
 //
-// cp_pick (round 5, `profiles/r05/ab/ab10_*`): form 2 builds the staying value with bit
-// operations — the leaving record's slot becomes the dummy by the sign-extended bit j of
-// its c (v_bfe_i32) OR-ed into c and AND-NOT-ed out of the value (v_bfi_b32) — and keeps
-// one compare for the mover (bit j set, top bit clear); form 3 drops that compare too: with
-// the dummy at c = 2^31 the mover is just bit j of c (j <= 28 since L < 2^29), and both
-// selects are v_bfi_b32 on sign-extended bits — six VALU per pick, no lane-mask write
-// (form 1: two compares, four selects, and the wait states between a compare and its
-// select).  All three move the same records: bit-identical outputs.
+// cp_pick: with the dummy at c = 2^31 the mover is just bit j of c (j <= 28 since L <
+// 2^29) and the leaving record's slot becomes the dummy by the sign-extended bit j of its c
+// (v_bfe_i32); both selects are v_bfi_b32 on sign-extended bits, no compare and no
+// lane-mask write.  A dummy's val is left as it was (the final pass writes +0.0 for any
+// dummy it outputs, cp_out), so the staying val needs no select: five VALU per pick.
 __device__ __forceinline__ uint64_t cp_pick(uint64_t self, uint64_t right, uint32_t j) {
     const uint32_t cs = (uint32_t)self, cr = (uint32_t)right;
-    if constexpr (FLTEE_CP_PICK == 4) {
-        // form 4: a dummy's val is left as it was (the final pass writes +0.0 for any dummy
-        // it outputs, cp_out), so the staying val needs no select: five VALU per pick.
-        // Round 5 A/B (`profiles/r05/ab/ab15_*`, bit-identical): compact_pass 431 -> 420 us
-        // at C5 (12.27 -> 12.23 ms), C3 0.1365 -> 0.1355 ms.
-        uint32_t lo, hi, e, em;
-        const uint32_t dmy = 0x80000000u;
-        asm("v_bfe_i32 %2, %4, %8, 1\n\t"        // e = ~0 iff self leaves
-            "v_bfe_i32 %3, %6, %8, 1\n\t"        // em = ~0 iff right moves in
-            "v_bfi_b32 %0, %2, %9, %4\n\t"       // stay c: the dummy's when self leaves
-            "v_bfi_b32 %0, %3, %6, %0\n\t"       // right's c if it moves in
-            "v_bfi_b32 %1, %3, %7, %5"             // right's val if it moves in, else self's
-            : "=&v"(lo), "=&v"(hi), "=&v"(e), "=&v"(em)
-            : "v"(cs), "v"((uint32_t)(self >> 32)), "v"(cr), "v"((uint32_t)(right >> 32)), "s"(j),
-              "s"(dmy));
-        return ((uint64_t)hi << 32) | lo;
-    }
-    if constexpr (FLTEE_CP_PICK == 3) {
-        uint32_t lo, hi, e, em;
-        const uint32_t dmy = 0x80000000u;
-        asm("v_bfe_i32 %2, %4, %8, 1\n\t"        // e = ~0 iff self leaves (bit j of its c)
-            "v_bfe_i32 %3, %6, %8, 1\n\t"        // em = ~0 iff right moves in
-            "v_bfi_b32 %0, %2, %9, %4\n\t"       // stay c: the dummy's when self leaves
-            "v_bfi_b32 %1, %2, 0, %5\n\t"        // stay val: +0.0 when self leaves
-            "v_bfi_b32 %0, %3, %6, %0\n\t"       // right's c if it moves in
-            "v_bfi_b32 %1, %3, %7, %1"             // right's val if it moves in
-            : "=&v"(lo), "=&v"(hi), "=&v"(e), "=&v"(em)
-            : "v"(cs), "v"((uint32_t)(self >> 32)), "v"(cr), "v"((uint32_t)(right >> 32)), "s"(j),
-              "s"(dmy));
-        return ((uint64_t)hi << 32) | lo;
-    }
-    if constexpr (FLTEE_CP_PICK == 2) {
-        uint32_t e, shi;
-        asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(e) : "v"(cs), "s"(j));
-        asm("v_bfi_b32 %0, %1, 0, %2" : "=v"(shi) : "v"(e), "v"((uint32_t)(self >> 32)));
-        const uint64_t stay = ((uint64_t)shi << 32) | (cs | e);
-        const uint32_t m = 1u << j;
-        return (cr & (m | 0x80000000u)) == m ? right : stay;
-    }
-    const bool mv = ((cr >> j) & ~(cr >> 31)) & 1u;
-    const bool st = !((cs >> j) & 1u);
-    return mv ? right : (st ? self : CP_DUMMY);
+    uint32_t lo, hi, e, em;
+    const uint32_t dmy = 0x80000000u;
+    asm("v_bfe_i32 %2, %4, %8, 1\n\t"        // e = ~0 iff self leaves
+        "v_bfe_i32 %3, %6, %8, 1\n\t"        // em = ~0 iff right moves in
+        "v_bfi_b32 %0, %2, %9, %4\n\t"       // stay c: the dummy's when self leaves
+        "v_bfi_b32 %0, %3, %6, %0\n\t"       // right's c if it moves in
+        "v_bfi_b32 %1, %3, %7, %5"             // right's val if it moves in, else self's
+        : "=&v"(lo), "=&v"(hi), "=&v"(e), "=&v"(em)
+        : "v"(cs), "v"((uint32_t)(self >> 32)), "v"(cr), "v"((uint32_t)(right >> 32)), "s"(j),
+          "s"(dmy));
+    return ((uint64_t)hi << 32) | lo;
 }
 
-// the value a final pass outputs for slot record r: +0.0 for a dummy (form 4 leaves a
+// the value a final pass outputs for slot record r: +0.0 for a dummy (cp_pick leaves a
 // dummy's val as it was; a position-sharded range outputs +0.0 where it holds no index)
-__device__ __forceinline__ float cp_out(uint64_t r) {
-    if constexpr (FLTEE_CP_PICK == 4) return ((uint32_t)r >> 31) ? 0.0f : rec_val(r);
-    return rec_val(r);
-}
+__device__ __forceinline__ float cp_out(uint64_t r) { return ((uint32_t)r >> 31) ? 0.0f : rec_val(r); }
 
 typedef unsigned int cp_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int cp_u32x4 __attribute__((ext_vector_type(4)));
 
-// The levels of one tile with its shape known at compile time (FLTEE_CP_CT): G levels on rows
+// The levels of one tile with its shape known at compile time: G levels on rows
 // of 2^LW residues, SH = S + H rows in the tile.  The level loop unrolls, so every LDS slot
 // of a round is an immediate offset off one per-lane address, and the range test (f < lim)
 // is decided at compile time for every slot but those of the last rows: only the picks'
@@ -157,7 +92,7 @@ typedef unsigned int cp_u32x4 __attribute__((ext_vector_type(4)));
 template <int NT, int PER, int G, int LW, int SH, int G0 = 0>
 __device__ __forceinline__ void cp_levels_ct(uint64_t *sm, uint32_t j0, uint32_t t) {
     if constexpr (G0 < G) {
-        constexpr bool two = FLTEE_CP_TWO && G0 + 1 < G;
+        constexpr bool two = G0 + 1 < G;
         constexpr uint32_t stepf = (1u << LW) << G0;
         constexpr uint32_t gl = two ? G0 + 1 : G0;
         constexpr uint32_t lim = ((uint32_t)SH - ((2u << gl) - 1)) << LW;
@@ -198,7 +133,7 @@ __device__ __forceinline__ void cp_levels_ct(uint64_t *sm, uint32_t j0, uint32_t
 // levels keep the one-slot-per-lane assignment.
 // NH (no halo): the tile is its residue group's only band (S = every row), so the rows a
 // halo would hold lie past L — dummies that never move: they are neither loaded nor kept in
-// LDS, a level reading one gets the dummy (compact_levels; FLTEE_CP_NOHALO).
+// LDS, a level reading one gets the dummy (compact_levels).
 template <int NT, int PER, bool FIRST, int FINAL, int MINB = 1, bool V2 = false, int CG = 0, int CLW = 0,
           int CSH = 0, bool NH = false>
 __global__ __launch_bounds__(NT, MINB) void compact_pass(const uint64_t *__restrict__ src,
@@ -273,7 +208,7 @@ __global__ __launch_bounds__(NT, MINB) void compact_pass(const uint64_t *__restr
         }
         __syncthreads();
         const uint32_t next = tile + gridDim.x;
-        if (!FLTEE_CP_SKIP_SELF || next < ntiles) prefetch(next < ntiles ? next : tile);
+        if (next < ntiles) prefetch(next);  // a block on its last tile prefetches nothing
         // Levels two per LDS round: z[f] = pick_{g+1}(pick_g(x[f], x[f+s]),
         // pick_g(x[f+2s], x[f+3s])) — 4 reads + 1 write per record per two levels
         // instead of 2 + 1 per level (ds_write_b64 costs ~3x a ds_read_b64), half the
@@ -289,7 +224,7 @@ __global__ __launch_bounds__(NT, MINB) void compact_pass(const uint64_t *__restr
         for (uint32_t g = 0; g < G;) {
             const uint32_t stepf = W << g;
             const uint32_t j = j0 + g;
-            const bool two = FLTEE_CP_TWO && g + 1 < G;
+            const bool two = g + 1 < G;
             const uint32_t gl = two ? g + 1 : g;
             const uint32_t lim0 = (S + H - ((2u << gl) - 1)) << logW;
             const uint32_t lim = NH && used < lim0 ? used : lim0;
@@ -361,39 +296,24 @@ __global__ __launch_bounds__(NT, MINB) void compact_pass(const uint64_t *__restr
     }
 }
 
-// Resident 512-lane blocks per CU for the passes after the first: 3 (default) asks hipcc
-// for 6 waves per SIMD (launch_bounds' 2nd argument = min waves per EU: <= 80 VGPRs).
-// A/B at C5: 497 vs 534 us per middle pass, 499 vs 570 us for the last; the first pass
-// (more live state) spills at that bound (868 vs 751 us), so it keeps 2.
-// Round 3: the kernels no longer spill (54 VGPRs, the lane id re-read where used), so the
-// first pass may take as many blocks as the later ones (FLTEE_COMPACT_FIRST_BLOCKS), and 4
-// blocks (8 waves per SIMD, <= 64 VGPRs) fit too (FLTEE_COMPACT_BLOCKS; A/B builds).
-#ifndef FLTEE_COMPACT_BLOCKS
-#define FLTEE_COMPACT_BLOCKS 4
-#endif
-#ifndef FLTEE_COMPACT_FIRST_BLOCKS
-#define FLTEE_COMPACT_FIRST_BLOCKS 4
-#endif
-constexpr int kCompactBlocks = FLTEE_COMPACT_BLOCKS;
-constexpr int kCompactFirstBlocks = FLTEE_COMPACT_FIRST_BLOCKS;
+// Resident 512-lane blocks per CU, first pass and later ones: 4 (launch_bounds' 2nd argument
+// = 8 waves per SIMD, <= 64 VGPRs).  The kernels run in 54 VGPRs since round 3 (the lane id
+// re-read where used); 2 and 3 blocks were kept while they spilled (`profiles/r03/ab/`).
+constexpr int kCompactBlocks = 4;
+constexpr int kCompactFirstBlocks = 4;
 // fltee_debug_set_compact_variant (A/B): 1 = 32 KiB tiles (default), 0 = 64 KiB tiles
 // (1024 lanes x 8), 2 = 32 KiB first pass + 64 KiB strided passes (1024 lanes x 8, one
 // block per CU: 6 levels per pass, 4 passes instead of 5 at C5; 512 x 16 spills)
 static int g_compact_variant = 1;
 void set_compact_variant(int v) { g_compact_variant = v; }
 
-#ifndef FLTEE_COMPACT_V2
-#define FLTEE_COMPACT_V2 1
-#endif
 // the last levels as one pass over the output prefix (compact_levels) on arrays of at most
-// 2^FLTEE_CP_TAIL_MERGE records (0: never).  Round 5 A/B (`profiles/r05/ab/ab15_*`,
+// 2^kCpTailMerge records.  Round 5 A/B (`profiles/r05/ab/ab15_*`,
 // bit-identical): C3 0.1365 -> 0.1319 ms, MLP-MNIST n = 30 advanced 0.088 -> 0.082 ms (a
 // launch less on arrays that stay in the caches); C5 12.27 -> 12.55 ms (the merged pass
 // computes 8 levels over 14x the slots it outputs, 1.07 ms against 0.75 for the two passes
 // it replaces), so large arrays keep the separate passes.
-#ifndef FLTEE_CP_TAIL_MERGE
-#define FLTEE_CP_TAIL_MERGE 21
-#endif
+constexpr uint32_t kCpTailMerge = 21;
 template <int NT, int PER, int MINB = 1>
 static hipError_t launch_pass(bool first, int fin, unsigned grid, hipStream_t s, const uint64_t *src,
                               uint64_t *dst, uint32_t L, uint32_t d, uint32_t j0, uint32_t G,
@@ -407,13 +327,13 @@ static hipError_t launch_pass(bool first, int fin, unsigned grid, hipStream_t s,
                        src, dst, L, d, j0, G, logW, S, rows, ngroups, coef, out, ntiles)
     // 16-B slot pairs: rows of >= 2 residues (or a contiguous tile of an even S: the
     // converted first pass), L even, both buffers 16-B aligned
-    const bool v2 = FLTEE_COMPACT_V2 && !first && (logW >= 1 || S % 2 == 0) && L % 2 == 0 &&
+    const bool v2 = !first && (logW >= 1 || S % 2 == 0) && L % 2 == 0 &&
                     (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
-    // the tile shapes of C5's passes with compile-time levels (FLTEE_CP_CT): the converted
+    // the tile shapes of C5's passes with compile-time levels (cp_levels_ct): the converted
     // first pass (9 levels, contiguous, S + H = 4,095) and the strided middle ones (5 levels
     // on rows of 16, one 256-row band)
     const uint32_t sh = S + (1u << G) - 1;
-    if constexpr (FLTEE_CP_CT && NT * PER == 4096) {
+    if constexpr (NT * PER == 4096) {
         if (!first && v2 && fin == 0) {
             if (G == 9 && logW == 0 && sh == 4095) { CP_GO_CT(true, 9, 0, 4095); return hipGetLastError(); }
             if (G == 5 && logW == 4 && sh == 256) { CP_GO_CT(true, 5, 4, 256); return hipGetLastError(); }
@@ -422,7 +342,7 @@ static hipError_t launch_pass(bool first, int fin, unsigned grid, hipStream_t s,
 #define CP_GO_NH(X, V)                                                                           \
     FLTEE_LAUNCH((compact_pass<NT, PER, false, X, MINB, V, 0, 0, 0, true>), dim3(grid), dim3(NT), 0, s, \
                        src, dst, L, d, j0, G, logW, S, rows, ngroups, coef, out, ntiles)
-    if (FLTEE_CP_NOHALO && nh && !first) {  // one band: no halo rows (compact_pass NH)
+    if (nh && !first) {  // one band: no halo rows (compact_pass NH)
         if (v2) {
             if (fin == 0) CP_GO_NH(0, true); else if (fin == 1) CP_GO_NH(1, true); else CP_GO_NH(2, true);
         } else {
@@ -470,7 +390,7 @@ static hipError_t compact_levels(uint64_t *src, uint64_t *tmp, size_t L, size_t 
         const uint32_t rows = (uint32_t)rows64;
         uint32_t logW, S;
         bool nohalo = false;
-        // The last levels in one pass over the output prefix (FLTEE_CP_TAIL_MERGE): the final
+        // The last levels in one pass over the output prefix (kCpTailMerge): the final
         // pass writes out[p] for p < d only, i.e. rows < ceil(d / 2^j0) of each residue
         // class, and a record reaches row r from rows < r + 2^G.  So one band of those rows +
         // 2^G - 1 halo rows per residue group covers every level left (G up to 10) when it
@@ -478,7 +398,7 @@ static hipError_t compact_levels(uint64_t *src, uint64_t *tmp, size_t L, size_t 
         // tiles, 100 output + 1,023 halo rows of 2 residues each, instead of two.
         bool tail = false;
         uint32_t tcap = CAP;
-        if (FLTEE_CP_TAIL_MERGE && L <= ((size_t)1 << FLTEE_CP_TAIL_MERGE) && j0 > 0 && nlev - j0 > G &&
+        if (L <= ((size_t)1 << kCpTailMerge) && j0 > 0 && nlev - j0 > G &&
             nlev - j0 <= 10) {
             const uint32_t Gt = nlev - j0, Ht = (1u << Gt) - 1;
             const uint64_t so = (d + ((uint64_t)1 << j0) - 1) >> j0;  // output rows
@@ -509,24 +429,23 @@ static hipError_t compact_levels(uint64_t *src, uint64_t *tmp, size_t L, size_t 
             if (converted) S &= ~1u;  // even: 16-B slot pairs
         } else {
             logW = 4;  // 16 residues = 128-B row segments
-            // One band: widen the rows instead.  Its halo rows lie past L (dummies).  With
-            // FLTEE_CP_NOHALO the tile drops them (compact_pass NH: a select per level read)
-            // where that widens the rows; else they stay (they load nothing), and a band of
-            // 16-residue rows is padded to the full 256-row tile — rows past L again — so
-            // the compile-time levels run it (FLTEE_CP_CT; C5's levels 19-23: 488 -> ~400 us).
-            const bool nh_ok = FLTEE_CP_NOHALO && kCompactBlocks >= 4;
+            // One band: widen the rows instead.  Its halo rows lie past L (dummies).  The
+            // tile drops them (compact_pass NH: a select per level read) where that widens
+            // the rows; else they stay (they load nothing), and a band of 16-residue rows is
+            // padded to the full 256-row tile — rows past L again — so the compile-time
+            // levels run it (C5's levels 19-23: 488 -> ~400 us).
             const bool fits = rows + H <= CAP >> logW;
-            if (fits || (nh_ok && rows <= CAP >> logW)) {
+            if (fits || rows <= CAP >> logW) {
                 uint32_t lw = logW, lwn = logW;
                 while (lw < j0 && ((rows + H) << (lw + 1)) <= CAP) ++lw;
                 while (lwn < j0 && (rows << (lwn + 1)) <= CAP) ++lwn;
-                if (nh_ok && (!fits || lwn > lw)) {
+                if (!fits || lwn > lw) {
                     logW = lwn;
                     S = rows;
                     nohalo = true;
                 } else {
                     logW = lw;
-                    S = lw == 4 && FLTEE_CP_CT && FLTEE_CP_PAD_BAND ? (CAP >> 4) - H : rows;
+                    S = lw == 4 ? (CAP >> 4) - H : rows;
                 }
             } else {
                 S = (CAP >> logW) - H;
@@ -557,17 +476,9 @@ static hipError_t compact_levels(uint64_t *src, uint64_t *tmp, size_t L, size_t 
         const unsigned res = !wide ? 256u * (unsigned)blk : 256u;
         const unsigned grid = (unsigned)(ntiles < res ? ntiles : res);
         const hipError_t e =
-            !wide ? (blk >= 4
-                         ? launch_pass<512, 8, 8>(j0 == 0 && !converted, fin, grid, s, cur, oth, (uint32_t)L,
-                                                  (uint32_t)d, j0, G, logW, S, rows, ngroups, coef,
-                                                  out, (uint32_t)ntiles, nohalo)
-                     : blk == 3
-                         ? launch_pass<512, 8, 6>(j0 == 0 && !converted, fin, grid, s, cur, oth, (uint32_t)L,
-                                                  (uint32_t)d, j0, G, logW, S, rows, ngroups, coef,
-                                                  out, (uint32_t)ntiles)
-                         : launch_pass<512, 8>(j0 == 0 && !converted, fin, grid, s, cur, oth, (uint32_t)L,
-                                               (uint32_t)d, j0, G, logW, S, rows, ngroups, coef, out,
-                                               (uint32_t)ntiles))
+            !wide ? launch_pass<512, 8, 8>(j0 == 0 && !converted, fin, grid, s, cur, oth, (uint32_t)L,
+                                           (uint32_t)d, j0, G, logW, S, rows, ngroups, coef, out,
+                                           (uint32_t)ntiles, nohalo)
                   : launch_pass<1024, 8>(j0 == 0 && !converted, fin, grid, s, cur, oth, (uint32_t)L, (uint32_t)d, j0,
                                          G, logW, S, rows, ngroups, coef, out, (uint32_t)ntiles);
         if (e != hipSuccess) return e;
@@ -597,7 +508,7 @@ hipError_t launch_compact_extract(uint64_t *src, uint64_t *tmp, size_t L, size_t
 // the compaction reads: whether p is its run's representative (the run's last
 // position: idx[p+1] != idx[p], or p = L-1) with idx < d, and then the run's sum —
 // v_head, (v_head + v_next), ... left to right, the enclave's order.  Each lane walks
-// back lim = halo + 1 slots from its own and forward through them (FLTEE_FC_FIXED_WALK
+// back lim = halo + 1 slots from its own and forward through them (the fixed walk
 // below), so every run of <= lim entries gets the enclave's sum bit for bit.  The folded
 // array (1 GB at C5) is never written and read back.  Dummies and non-representatives are
 // never selected by the compaction, so their contents do not matter.
@@ -614,17 +525,11 @@ hipError_t launch_compact_extract(uint64_t *src, uint64_t *tmp, size_t L, size_t
 // depend on the other tiles' progress only), and the grid never exceeds the blocks that
 // fit on the chip at once (a tile only waits for tiles of lower index, already running),
 // with a bounded wait that reports FLTEE_DEV_ERR_LAUNCH instead of hanging.
-// Resident blocks per CU of the fused first pass, and whether a block prefetches its next
-// window during the fold.  Round 3 (A/B in one process, `profiles/r03/ab/ab18_fold_blocks_*`):
-// three blocks without the prefetch ran C5's pass fastest then.  Round 6: with the long-run
-// steps (three LDS arrays, the look-back) three blocks' 80 VGPRs spill 20-50 registers;
-// two blocks (128 VGPRs) do not (`profiles/r06/ab/`).
-#ifndef FLTEE_FC_BLOCKS
-#define FLTEE_FC_BLOCKS 2
-#endif
-#ifndef FLTEE_FC_PF
-#define FLTEE_FC_PF 0
-#endif
+// Resident blocks per CU of the fused first pass: 2 (128 VGPRs).  Round 6: with the long-run
+// steps (three LDS arrays, the look-back) three blocks' 80 VGPRs spill 20-50 registers
+// (`profiles/r06/ab/`).  A block loads its window when it reaches the tile; prefetching the
+// next one during the fold was slower (`profiles/r03/ab/ab18_fold_blocks_*`).
+constexpr int kFcBlocks = 2;
 // Round 5, measured and not kept: 8,192-record windows (1,024 lanes x 8, one block per CU)
 // for the wide-halo arrays — one 1,024-lane block per CU has too few waves to hide the
 // window load that three 512-lane blocks hide (`profiles/r05/ab/ab3_fold_window8192_c5_
@@ -642,27 +547,13 @@ hipError_t launch_compact_extract(uint64_t *src, uint64_t *tmp, size_t L, size_t
 // where the streaming fold's launch and latency cost more than the longer walk (MLP-MNIST
 // n = 300, lim 301: 0.101 vs 0.138 ms, `profiles/r05/ab/ab12_*`); 320 keeps three windows
 // + sums per CU in the 160 KiB of LDS.
-#ifndef FLTEE_FC_WALK_MAX
-#define FLTEE_FC_WALK_MAX 128
-#endif
-#ifndef FLTEE_FC_WALK_MAX_SMALL
-#define FLTEE_FC_WALK_MAX_SMALL 320
-#endif
-constexpr uint32_t kFixedWalkMax = FLTEE_FC_WALK_MAX;
-constexpr uint32_t kFixedWalkMaxSmall = FLTEE_FC_WALK_MAX_SMALL;
-#ifndef FLTEE_FC_LB
-#define FLTEE_FC_LB 1
-#endif
+constexpr uint32_t kFixedWalkMax = 128;
+constexpr uint32_t kFixedWalkMaxSmall = 320;
 // tiles per CU the per-lane slot count aims for (the fewest slots with at most this many)
-#ifndef FLTEE_FC_TILES_PER_CU
-#define FLTEE_FC_TILES_PER_CU 1
-#endif
-// the look-back's first-round words loaded before the compaction levels (1) or after (0).
-// Round 6 A/B (`profiles/r06/ab/ab2_*`): 28.9 vs 27.1 us per C3 pass — the 12 VGPRs held
-// across the levels cost more than the load latency they hide
-#ifndef FLTEE_FC_LBPRE
-#define FLTEE_FC_LBPRE 0
-#endif
+constexpr uint32_t kFcTilesPerCu = 1;
+// (The look-back's first-round words loaded before the compaction levels: 28.9 vs 27.1 us
+// per C3 pass, rejected — the 12 VGPRs held across the levels cost more than the load
+// latency they hide, `profiles/r06/ab/ab2_*`.)
 // the bounded look-back wait: polls of ~0.25 us (about a quarter second in all)
 constexpr uint32_t kFcSpinMax = 1u << 20;
 
@@ -712,8 +603,11 @@ __device__ __forceinline__ bool fc_have(const uint64_t *w, uint32_t epoch, FoldA
            (uint32_t)(w[2] >> 34) == epoch;
 }
 
-// pre: this thread's first-round predecessor (tile - 1 - t) words, loaded ahead (inc[3],
-// agg[3]): used when they are already this epoch's, else polled again
+// pre: six words the first round tests before it polls.  DEAD: the caller passes zeros,
+// which never carry a launch's epoch (>= 1), so the first round always polls — what is
+// left of the rejected early load (`profiles/r06/ab/ab2_*`).  Taking `pre` and the
+// first-round test out changes the kernel's code, so it goes with the look-back redesign
+// ("A/B builds and their knobs").
 template <int NW>
 __device__ FoldAgg fc_lookback(FcLb *lb, uint32_t tile, uint32_t epoch, uint32_t t,
                                uint32_t *status, FoldAgg *sh, uint32_t *shf, const uint64_t *pre) {
@@ -791,8 +685,8 @@ __device__ FoldAgg fc_lookback(FcLb *lb, uint32_t tile, uint32_t epoch, uint32_t
     return run;
 }
 
-template <int NT, int PER, int FINAL, int XMAX, int BPC = FLTEE_FC_BLOCKS>
-__global__ __launch_bounds__(NT, BPC * NT >= 1024 ? BPC * NT / 256 : 1) void fold_compact_first(const uint64_t *__restrict__ A,
+template <int NT, int PER, int FINAL, int XMAX>
+__global__ __launch_bounds__(NT, kFcBlocks * NT >= 1024 ? kFcBlocks * NT / 256 : 1) void fold_compact_first(const uint64_t *__restrict__ A,
                                                             uint64_t *__restrict__ dst, uint32_t L,
                                                             uint32_t M, uint32_t d, uint32_t G,
                                                             uint32_t S, uint32_t Hr,
@@ -832,17 +726,14 @@ __global__ __launch_bounds__(NT, BPC * NT >= 1024 ? BPC * NT / 256 : 1) void fol
     };
     uint32_t tile = blockIdx.x;
     if (tile >= ntiles) return;
-    if (FLTEE_FC_PF) prefetch(tile);
     for (;;) {
-        if (!FLTEE_FC_PF) prefetch(tile);
+        prefetch(tile);
         const long long a = (long long)tile * S, wlo = a - (long long)Hr;
 #pragma unroll
         for (uint32_t i = 0; i < PER + XMAX; ++i)
             if (t + i * NT < Wn) win[t + i * NT] = pf[i];
         __syncthreads();
         const uint32_t next = tile + gridDim.x;
-        if (FLTEE_FC_PF && (!FLTEE_CP_SKIP_SELF || next < ntiles))
-            prefetch(next < ntiles ? next : tile);  // lands while this tile folds and compacts
         // Each lane owns window slots [x0, x0 + chunk) and computes, for each, the
         // in-order sum of its run up to that slot: a walk from x0 - lim (every run of <= lim
         // entries of an owned slot starts after it), lim + chunk steps whatever the data, no
@@ -983,32 +874,20 @@ __global__ __launch_bounds__(NT, BPC * NT >= 1024 ? BPC * NT / 256 : 1) void fol
         uint64_t *sm = win;
 #pragma unroll
         for (uint32_t i = 0; i < PER; ++i) sm[t + i * NT] = v[i];
-        // the look-back's first-round words, loaded now: they arrive while the levels run
-        uint64_t lw[6] = {0, 0, 0, 0, 0, 0};
-        {
-            const long long p1 = (long long)tile - 1 - (long long)t;
-            if (FLTEE_FC_LB && FLTEE_FC_LBPRE && p1 >= 0) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    lw[i] = __hip_atomic_load(&lb[p1].inc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    lw[3 + i] = __hip_atomic_load(&lb[p1].agg[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
+        // fc_lookback's `pre`: dead, always zeros (see fc_lookback)
+        const uint64_t lw[6] = {0, 0, 0, 0, 0, 0};
         __syncthreads();
         // the first G levels, exactly compact_pass's (contiguous: W = 1, j0 = 0); all nine at
-        // compile time when the array has that many (FLTEE_CP_CT, cp_levels_ct)
+        // compile time when the array has that many (cp_levels_ct)
         bool lv_done = false;
-        if constexpr (FLTEE_CP_CT) {
-            if (G == 9 && S + H == CAP) {
-                cp_levels_ct<NT, PER, 9, 0, (int)CAP>(sm, 0u, t);
-                lv_done = true;
-            }
+        if (G == 9 && S + H == CAP) {
+            cp_levels_ct<NT, PER, 9, 0, (int)CAP>(sm, 0u, t);
+            lv_done = true;
         }
         uint64_t nv[PER];
         for (uint32_t g = 0; g < (lv_done ? 0u : G);) {
             const uint32_t stepf = 1u << g;
-            const bool two = FLTEE_CP_TWO && g + 1 < G;
+            const bool two = g + 1 < G;
             const uint32_t gl = two ? g + 1 : g;
             const uint32_t lmt = S + H - ((2u << gl) - 1);
             if (two) {
@@ -1037,13 +916,10 @@ __global__ __launch_bounds__(NT, BPC * NT >= 1024 ? BPC * NT / 256 : 1) void fol
             __syncthreads();
             g += two ? 2 : 1;
         }
-        // the carry from in front of the window (decoupled look-back; FLTEE_FC_LB=0: none,
-        // an A/B of its cost only) into the window head run's record, if it began before
-        FoldAgg wc = fa_empty();
-        if (FLTEE_FC_LB) {
-            wc = fc_lookback<NW>(lb, tile, epoch, t, status, lb_sh, lb_shf, lw);
-            if (t == 0) fc_put(lb[tile].inc, fa_combine(wc, agg_s), epoch);
-        }
+        // the carry from in front of the window (decoupled look-back) into the window head
+        // run's record, if it began before
+        const FoldAgg wc = fc_lookback<NW>(lb, tile, epoch, t, status, lb_sh, lb_shf, lw);
+        if (t == 0) fc_put(lb[tile].inc, fa_combine(wc, agg_s), epoch);
         const bool wok = (wc.fl & kFsPiece) && wc.K == kw0_s;
         const uint32_t fx = fix_s;
 #pragma unroll
@@ -1082,8 +958,7 @@ static hipError_t fc_launch(uint64_t ntiles, size_t lds, hipStream_t s, const ui
                             float coef, float *out, uint32_t lim, FcLb *lb, uint32_t epoch,
                             uint32_t *status) {
     constexpr int NT = 512;
-    constexpr int BPC = FLTEE_FC_BLOCKS;
-    auto kern = fold_compact_first<NT, PER, F, X, BPC>;
+    auto kern = fold_compact_first<NT, PER, F, X>;
     // the grid never exceeds the blocks resident at once (the look-back waits for tiles of
     // lower index only: they are running), whatever the occupancy turns out to be
     static int resident = 0;
@@ -1097,7 +972,7 @@ static hipError_t fc_launch(uint64_t ntiles, size_t lds, hipStream_t s, const ui
             hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, NT, lds) !=
                 hipSuccess)
             return hipErrorLaunchFailure;
-        if (per_cu > BPC) per_cu = BPC;
+        if (per_cu > kFcBlocks) per_cu = kFcBlocks;
         resident = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
         res_lds = lds;
     }
@@ -1153,7 +1028,7 @@ static bool fc_shape(size_t M, size_t L, size_t d, size_t halo, FcShape &o) {
     o.per = 8;
     for (uint32_t p : {4u, 6u}) {
         if (NT * p <= 2 * H) continue;  // the halo rows would swamp the tile
-        if ((L + NT * p - H - 1) / (NT * p - H) <= 256 * FLTEE_FC_TILES_PER_CU) {
+        if ((L + NT * p - H - 1) / (NT * p - H) <= 256 * kFcTilesPerCu) {
             o.per = p;
             break;
         }
@@ -1164,7 +1039,7 @@ static bool fc_shape(size_t M, size_t L, size_t d, size_t halo, FcShape &o) {
     // the window, the walks' run sums and the run partials beside it; the resident blocks
     // per CU must fit the 160 KiB LDS (lim <= 320: 71 KiB a block)
     const size_t lds = (o.Hr + CAP + 1) * 12;  // the window (8 B a slot), its sums (4 B)
-    return lds * FLTEE_FC_BLOCKS <= 160 * 1024 && lds <= 80 * 1024;
+    return lds * kFcBlocks <= 160 * 1024 && lds <= 80 * 1024;
 }
 
 size_t fc_lookback_bytes(size_t M, size_t L, size_t d, size_t halo) {

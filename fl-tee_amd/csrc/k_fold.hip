@@ -285,9 +285,8 @@ __global__ __launch_bounds__(64) void fold_stream_kernel(const uint64_t *__restr
 
 size_t fold_context(size_t halo) { return (halo + FS_W - 1) / FS_W * FS_W; }
 
-#ifndef FLTEE_FS_DOUBLE_WAVES
-#define FLTEE_FS_DOUBLE_WAVES 1024
-#endif
+// waves that must remain for fold_chunk's last doubling of the chunk length
+constexpr size_t kFsDoubleWaves = 1024;
 // The chunk length of a fold over span positions with this halo (0: the one-lane walk
 // over the whole array, origin = pbase = 0 only).
 static size_t fold_chunk(size_t span, size_t Hr) {
@@ -298,7 +297,7 @@ static size_t fold_chunk(size_t span, size_t Hr) {
     while (C > FS_W && span / (64 * C) < 1024) C >>= 1;
     // one doubling more while >= 1024 waves remain: less halo re-read (C5: 2048 instead
     // of 1024, 620 vs 643 us; 4096: 700 us, 8192: 1220 us — too few waves in flight)
-    if (C >= Hr && span / (64 * 2 * C) >= FLTEE_FS_DOUBLE_WAVES) C <<= 1;
+    if (C >= Hr && span / (64 * 2 * C) >= kFsDoubleWaves) C <<= 1;
     return C;
 }
 

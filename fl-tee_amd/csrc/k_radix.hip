@@ -35,11 +35,6 @@ constexpr int kCsItems = 8;                // records per lane per tile
 constexpr int kCsTile = kCsNT * kCsItems;  // records per tile
 constexpr int kCsGroups = kCsItems * (kCsNT / 64);  // (round, wave) groups per tile
 constexpr int kCsBins = 256;
-// FLTEE_CS_STAGE: cs_scatter stages the tile in LDS and writes it out in sorted order (1) or
-// scatters each record straight from its registers (0) — A/B (scripts/ab_build.sh)
-#ifndef FLTEE_CS_STAGE
-#define FLTEE_CS_STAGE 1
-#endif
 
 struct CsPlan {
     uint32_t passes = 0, width = 0;
@@ -162,7 +157,7 @@ __global__ __launch_bounds__(kCsNT) void cs_scatter(const uint64_t *__restrict__
     __shared__ uint32_t tile_at[kCsBins];         // the tile's first slot per digit (global)
     __shared__ uint32_t loc_at[kCsBins];          // ... and inside the tile's staged order
     __shared__ uint32_t part[kCsNT / 64];
-    __shared__ uint64_t stage[FLTEE_CS_STAGE ? kCsTile : 1];  // the tile's records, sorted
+    __shared__ uint64_t stage[kCsTile];  // the tile's records, sorted
     const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const uint32_t mask = (1u << width) - 1u;
     for (int g = 0; g < kCsGroups; ++g) grp[g][t] = 0;
@@ -190,21 +185,6 @@ __global__ __launch_bounds__(kCsNT) void cs_scatter(const uint64_t *__restrict__
         if (live && (peers & lt) == 0) grp[r * (kCsNT / 64) + wv][dig[r]] = (uint16_t)__popcll(peers);
     }
     __syncthreads();
-    if constexpr (!FLTEE_CS_STAGE) {  // straight from the registers: global group offsets
-        __shared__ uint32_t gofs[kCsGroups][kCsBins];
-        uint32_t run = t <= mask ? tile_at[t] : 0u;
-#pragma unroll
-        for (int g = 0; g < kCsGroups; ++g) {
-            gofs[g][t] = run;
-            run += grp[g][t];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < kCsItems; ++r)
-            if (base + (uint32_t)r * kCsNT + t < n)
-                dst[gofs[r * (kCsNT / 64) + wv][dig[r]] + rank[r]] = rec[r];
-        return;
-    }
     // lane t = digit t: exclusive scan of its counts over the groups in position order, then
     // of the digits' tile totals (the staged order: digit by digit, stable within a digit)
     uint32_t tot;

@@ -1,7 +1,9 @@
 #!/bin/bash
-# An A/B build of the library with compile-time overrides of the tuning constants
-# (the product library has no runtime switches):
-#   [ONLY="k_bitonic k_fold"] scripts/ab_build.sh NAME -DFLTEE_SORT_LATEPF_KEY=1 ...
+# An A/B build of the library with compile-time -D overrides (the product library has no
+# runtime switches).  The source carries no standing knobs: an experiment adds its own
+# `#ifndef FLTEE_<KNOB>` on its branch and removes it with the change that records the
+# outcome ("A/B builds").  With such a knob in the source:
+#   [ONLY="k_bitonic k_fold"] scripts/ab_build.sh NAME -DFLTEE_<KNOB>=1 ...
 # -> fl-tee_amd/lib/ab/libfltee_agg_NAME.so, loaded by a run with FLTEE_LIB=<that path>
 #    (scripts/ab_env.py c5 FLTEE_LIB=fl-tee_amd/lib/ab/libfltee_agg_NAME.so)
 # ONLY: the sources the overrides touch; the other objects are copied from the product
