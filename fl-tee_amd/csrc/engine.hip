@@ -379,6 +379,14 @@ static hipError_t nips19_shuffle_aggregate(DeviceCtx *c, uint64_t *A, size_t M, 
 static bool g_advanced_compaction = true;  // fltee_debug_set_advanced_compaction
 static bool g_nips19_fused_select = true;  // fltee_debug_set_nips19_fused_select (A/B)
 
+// the positions run_advanced's separate fold covers in front of the compaction, which
+// reads [0, L) only: up to the first pad (position L is read as the run-end test of
+// L - 1), not the pads after it
+static size_t advanced_fold_span(size_t L, size_t M) {
+    const size_t mf = (L + 1 + 15) / 16 * 16;
+    return mf > M ? M : mf;
+}
+
 static hipError_t run_advanced(DeviceCtx *c, const void *rec, size_t n, size_t k, size_t d,
                                size_t k_req, size_t halo, float coef, float *out, bool acc,
                                uint32_t *status, hipStream_t s) {
@@ -408,10 +416,7 @@ static hipError_t run_advanced(DeviceCtx *c, const void *rec, size_t n, size_t k
         if (e != hipErrorNotSupported) return e;
     }
     if (fold_len == L && g_advanced_compaction) {
-        // the compaction reads [0, L) only: fold up to the first pad (position L is
-        // read as the run-end test of L - 1), not the pads after it
-        size_t mf = (L + 1 + 15) / 16 * 16;
-        if (mf > M) mf = M;
+        const size_t mf = advanced_fold_span(L, M);
         // the fold emits the compaction's first-pass form (no conversion there, 16-B pairs);
         // a one-entry array — d = 1 and no records — has nothing to fold: copied as the
         // enclave's folded array and converted by that pass
@@ -1010,6 +1015,8 @@ extern "C" fltee_status_t fltee_dp_noise_device(float *d_out, size_t d, float si
 
 namespace fltee {
 void set_dense_variant(int v); void set_compact_variant(int v); void set_fold_compact(int on);
+bool fold_compact_geometry(size_t M, size_t L, size_t d, size_t halo, uint64_t out[7]);
+bool fold_stream_geometry(size_t span, size_t fold_len, size_t halo, uint64_t out[5]);
 hipError_t launch_read_floor(const void *src, size_t bytes, uint32_t *sink, unsigned blocks, hipStream_t s);
 }
 // measurement hook (bench.py): a plain streaming read of `bytes` (16-B multiple) of d_src;
@@ -1048,6 +1055,21 @@ extern "C" void fltee_debug_set_aes_variant(int v) {
 }
 extern "C" void fltee_debug_set_swizzle(int on) { fltee::set_swizzle(on); }
 extern "C" void fltee_debug_set_fused_init(int on) { fltee::set_fused_init(on); }
+// test hook: how run_advanced folds a whole array of L = n * k + d entries (M = next_pow2(L),
+// fold_len == L, halo = the effective one: opts.fold_halo, or n) under the current A/B
+// settings.  Read-only, host only.  out[0]: 1 the fold fused into the compaction's first
+// pass, then {per, S, ntiles, lim, G, last pass (FINAL != 0), Hr}; 2 the streaming fold +
+// patch, 3 the one-lane walk, then {Hr, C, lanes, prefetch depth, patch blocks, span, 0}.
+extern "C" void fltee_debug_fold_geometry(size_t M, size_t L, size_t d, size_t halo, uint64_t *out) {
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (fltee::g_advanced_compaction && fltee::fold_compact_geometry(M, L, d, halo, out + 1)) {
+        out[0] = 1;
+        return;
+    }
+    const size_t span = fltee::g_advanced_compaction ? fltee::advanced_fold_span(L, M) : M;
+    out[0] = fltee::fold_stream_geometry(span, L, halo, out + 1) ? 2 : 3;
+    out[6] = span;
+}
 // A/B hook: 0 writes nips19's shuffled array out and selects in separate passes
 extern "C" void fltee_debug_set_nips19_fused_select(int on) { fltee::g_nips19_fused_select = on != 0; }
 // test hook: the fused-producer sort alone (gen 1: advanced, 2: nips19 with key seed),

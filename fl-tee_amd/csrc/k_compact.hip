@@ -1042,6 +1042,21 @@ static bool fc_shape(size_t M, size_t L, size_t d, size_t halo, FcShape &o) {
     return lds * kFcBlocks <= 160 * 1024 && lds <= 80 * 1024;
 }
 
+// test hook (fltee_debug_fold_geometry): the fused pass's geometry — {per, S, ntiles, lim, G,
+// whether it is the compaction's last pass, Hr}; false: not fused
+bool fold_compact_geometry(size_t M, size_t L, size_t d, size_t halo, uint64_t out[7]) {
+    FcShape o;
+    if (!fc_shape(M, L, d, halo, o)) return false;
+    out[0] = o.per;
+    out[1] = o.S;
+    out[2] = o.ntiles;
+    out[3] = o.lim;
+    out[4] = o.G;
+    out[5] = o.G == bitlen(L - d);
+    out[6] = o.Hr;
+    return true;
+}
+
 size_t fc_lookback_bytes(size_t M, size_t L, size_t d, size_t halo) {
     FcShape o;
     return fc_shape(M, L, d, halo, o) ? o.ntiles * sizeof(FcLb) : 0;

@@ -30,8 +30,9 @@
 // lane's first position a (a fixed address, whatever the data), either what the fold
 // left there or — for a lane with such a run — (key, carry + sum): a inside that run,
 // the one record of its key.  Exact (bit for bit) for every run inside one lane's walk,
-// the enclave's sum re-associated at the walk boundaries otherwise (north_star's 1e-6
-// relative tolerance for the aggregate).  No run-length limit, no rerun.
+// the enclave's sum re-associated at the walk boundaries otherwise (its bits whenever the
+// partial sums are exactly representable; else within the tree-height bound of
+// tests/longrun.py).  No run-length limit, no rerun.
 //
 // Layout: C >= Hr on large arrays (halo work <= 2x; small arrays take shorter
 // chunks, down to 16, to keep ~1024 waves in flight), so a lane walks a long chunk; the 64
@@ -305,6 +306,11 @@ static bool one_lane(size_t span, size_t fold_len, size_t halo, size_t origin, l
     return (halo + 1 >= span || halo + 1 >= fold_len) && origin == 0 && pbase == 0;
 }
 
+// Stages prefetched ahead by a streaming fold of this many waves.  About one wave per CU:
+// latency-bound, prefetch deeper (2 or 4 stages were no faster on the large arrays,
+// profiles/r01/ab/fold_chunk_depth*.jsonl)
+static int fold_depth(size_t blocks) { return blocks <= 256 ? 2 : 1; }
+
 size_t fold_lanes(size_t span, size_t fold_len, size_t halo, size_t origin, long long pbase) {
     if (one_lane(span, fold_len, halo, origin, pbase)) return 0;
     const size_t C = fold_chunk(span, fold_context(halo));
@@ -346,9 +352,7 @@ hipError_t launch_fold_range(const uint64_t *src, uint64_t *dst, size_t m, size_
     const size_t blocks = (lanes + 63) / 64;
     net_account((uint64_t)16 * span, "fold_stream_kernel", s);
     if (blocks > 0x7FFFFFFF) return hipErrorInvalidValue;
-    // about one wave per CU: latency-bound, prefetch deeper (2 or 4 stages were no faster
-    // on the large arrays, profiles/r01/ab/fold_chunk_depth*.jsonl)
-    const int depth = blocks <= 256 ? 2 : 1;
+    const int depth = fold_depth(blocks);
 #define FS_GO(D_, E_)                                                                              \
     FLTEE_LAUNCH((fold_stream_kernel<D_, E_>), dim3((unsigned)blocks), dim3(64), 0, s, src,  \
                        dst, (long long)m, (long long)origin, (long long)end, pbase,                \
@@ -455,6 +459,20 @@ __global__ __launch_bounds__(kFpNT) void fold_patch_kernel(const FoldSide *__res
 size_t fold_side_bytes(size_t span, size_t fold_len, size_t halo, size_t origin, long long pbase) {
     const size_t waves = (fold_lanes(span, fold_len, halo, origin, pbase) + 63) / 64;
     return waves * (64 * sizeof(FoldSide) + sizeof(FoldAgg));
+}
+
+// test hook (fltee_debug_fold_geometry): the streaming fold + patch over a whole array of
+// span positions — {Hr, C, lanes, prefetch depth, patch blocks}; false: the one-lane walk
+bool fold_stream_geometry(size_t span, size_t fold_len, size_t halo, uint64_t out[5]) {
+    if (one_lane(span, fold_len, halo, 0, 0)) return false;
+    const size_t Hr = fold_context(halo), C = fold_chunk(span, Hr);
+    const size_t lanes = (span + C - 1) / C;
+    out[0] = Hr;
+    out[1] = C;
+    out[2] = lanes;
+    out[3] = (uint64_t)fold_depth((lanes + 63) / 64);
+    out[4] = (lanes + kFpLanes - 1) / kFpLanes;
+    return true;
 }
 
 hipError_t launch_fold_range_total(const FoldSide *side, size_t lanes, FoldAgg *total,

@@ -210,3 +210,146 @@ def init_range(idx, val, d, pos, C):
     ini = (p >= nrec) & (p < nrec + d)
     out[ini] = (p[ini] - nrec).astype(np.uint64)
     return torch.from_numpy(out.view(np.int64).copy())
+
+
+# ---- the streaming fold + patch of a whole array, in the device's own association ----
+# (k_fold.hip fold_stream_kernel / fold_patch_kernel, common.h fa_combine; origin = pbase = 0,
+# no totals of earlier ranges.)  Aggregates are tuples of arrays (F, K, Q, fl).
+def _fa_empty(shape):
+    return (np.zeros(shape, np.uint32), np.zeros(shape, np.uint32), np.zeros(shape, np.float32),
+            np.zeros(shape, np.uint32))
+
+
+def _fa_combine(x, y):
+    """fa_combine exactly as in common.h, elementwise"""
+    xF, xK, xQ, xf = x
+    yF, yK, yQ, yf = y
+    xe, ye = (xf & 1) == 0, (yf & 1) == 0
+    yfull = (yf & 2) != 0
+    full = ((xf & 2) != 0) & yfull & (xK == yF)
+    r = (xF, yK, np.where(yfull & (yF == xK), (xQ + yQ).astype(np.float32), yQ),
+         np.where(full, 3, 1).astype(np.uint32))
+    return tuple(np.where(xe, b, np.where(ye, a, c)) for a, b, c in zip(x, y, r))
+
+
+def _fa_scan(g):
+    """the inclusive Hillis-Steele scan along the last axis (the wave's __shfl_up rounds,
+    fp_block_scan's LDS rounds): x = the element o in front (empty before the first)"""
+    n = g[0].shape[-1]
+    o = 1
+    while o < n:
+        e = _fa_empty(g[0].shape[:-1] + (o,))
+        g = _fa_combine(tuple(np.concatenate([ee, a[..., :-o]], axis=-1) for ee, a in zip(e, g)), g)
+        o <<= 1
+    return g
+
+
+def _fa_take(g, sel):
+    return tuple(a[sel] for a in g)
+
+
+def fold_stream_model(idx, val, fold_len, halo, Hr, C):
+    """fltee_fold_device(src = (idx, val), fold_len, halo) as the device computes it, bit for
+    bit, vectorised over lanes; Hr, C: the fold's geometry (fltee_debug_fold_geometry).
+    Lane j walks [a - Hr, a + C + 16), a = j C, in order (pre_idx / pre_val, the emitted
+    record of q - 1 at step q), keeps its FoldSide (the piece [a - Hr, a - Hr + C): first
+    key, last key, the run partial at its last position; the head run's sum when it ends in
+    the chunk), the 64 lanes of a wave scan their pieces (Hillis-Steele) into the wave
+    aggregate; the patch folds each of its 256 threads' slice of the wave aggregates in front
+    of the block left to right, scans the 256 partials, folds the thread's 4 lanes in order,
+    scans again, and writes (ck, run.Q + S) at a for every lane with a head run.  Returns
+    dst's (idx u32, val f32)."""
+    idx = np.ascontiguousarray(idx, np.uint32)
+    val = np.ascontiguousarray(val, np.float32)
+    m = len(idx)
+    assert Hr == (halo + 15) // 16 * 16 and Hr % 16 == 0 and C % 16 == 0
+    lanes = (m + C - 1) // C
+    waves = (lanes + 63) // 64
+    a = np.arange(waves * 64, dtype=np.int64) * C
+    b = a - Hr
+    live = a < m
+    MAXU = np.uint32(0xFFFFFFFF)
+
+    def rd(q):  # the record at q: zeros outside [0, m), as the kernel's window loads
+        ok = (q >= 0) & (q < m)
+        qc = np.clip(q, 0, m - 1)
+        return np.where(ok, idx[qc], np.uint32(0)), np.where(ok, val[qc], np.float32(0))
+
+    fp = np.maximum(b, 0)
+    pf_key = np.where(live & (fp < m), idx[np.clip(fp, 0, m - 1)], np.uint32(0)).astype(np.uint32)
+    in_head = live & (b - 1 >= 0) & (idx[np.clip(b - 1, 0, m - 1)] == pf_key)
+    pre_idx = np.full(len(a), 0xFFFFFFFE, np.uint32)
+    pre_val = np.zeros(len(a), np.float32)
+    cs = np.zeros(len(a), np.float32)
+    corr = np.zeros(len(a), bool)
+    piece = np.zeros(len(a), bool)
+    pk = np.zeros(len(a), np.uint32)
+    pq = np.zeros(len(a), np.float32)
+    oi, ov = idx.copy(), val.copy()
+    for step in range((Hr + C + 16) // 16 * 16):
+        q = b + step
+        e = q - 1
+        ci, v = rd(q)
+        pi, pv = rd(e)
+        eq = ci == pre_idx
+        copy = e >= fold_len
+        dmy = (q < fold_len) & eq
+        inchunk = (e >= a) & (e < a + C)
+        sup = in_head & ~copy & ~dmy & inchunk
+        du = dmy | sup
+        st = inchunk & live & (e < m)
+        es = e[st]
+        oi[es] = np.where(copy, pi, np.where(du, (MAXU - e.astype(np.uint32)), pre_idx))[st]
+        ov[es] = np.where(copy, pv, np.where(du, np.float32(0), pre_val))[st]
+        cs = np.where(sup, pre_val, cs)
+        corr |= sup
+        in_head = in_head & (dmy | (step == 0))
+        valid = q >= 0
+        nv = np.where(eq, (pre_val + v).astype(np.float32), v)
+        pre_val = np.where(valid, nv, pre_val)
+        pre_idx = np.where(valid, ci, pre_idx)
+        if step == C - 1:  # the piece's last position b + C - 1
+            piece, pk, pq = valid.copy(), pre_idx.copy(), pre_val.copy()
+    fl = np.where(live, piece * 1 + (piece & (pk == pf_key)) * 2, 0).astype(np.uint32)
+    corr &= live
+    side = (pf_key, pk, pq, fl)
+    wagg = _fa_take(_fa_scan(tuple(x.reshape(waves, 64) for x in side)), (slice(None), 63))
+    # the patch: blocks of 1,024 lanes = 256 threads x 4
+    nblk = (lanes + 1023) // 1024
+    pad = nblk * 1024 - len(a)
+    if pad > 0:
+        side = tuple(np.concatenate([x, np.zeros(pad, x.dtype)]) for x in side)
+        corr = np.concatenate([corr, np.zeros(pad, bool)])
+        cs = np.concatenate([cs, np.zeros(pad, np.float32)])
+    else:
+        side, corr, cs = tuple(x[:nblk * 1024] for x in side), corr[:nblk * 1024], cs[:nblk * 1024]
+    t = np.arange(256, dtype=np.int64)[None, :]
+    wb = (np.arange(nblk, dtype=np.int64) * 16)[:, None]  # the waves in front of the block
+    w0, w1 = wb * t // 256, wb * (t + 1) // 256
+    acc = _fa_empty((nblk, 256))
+    for i in range(int((w1 - w0).max()) if nblk else 0):
+        w = w0 + i
+        g = _fa_take(wagg, np.clip(w, 0, waves - 1))
+        nxt = _fa_combine(acc, g)
+        acc = tuple(np.where(w < w1, n_, a_) for n_, a_ in zip(nxt, acc))
+    carry = _fa_take(_fa_scan(acc), (slice(None), slice(255, 256)))  # allw (no earlier ranges)
+    sd = tuple(x.reshape(nblk, 256, 4) for x in side)
+    corr4, cs4 = corr.reshape(nblk, 256, 4), cs.reshape(nblk, 256, 4)
+    mine = _fa_empty((nblk, 256))
+    for i in range(4):
+        mine = _fa_combine(mine, _fa_take(sd, (slice(None), slice(None), i)))
+    inc = _fa_scan(mine)
+    e1 = _fa_empty((nblk, 1))
+    run = _fa_combine(tuple(np.broadcast_to(c, (nblk, 256)) for c in carry),
+                      tuple(np.concatenate([ee, x[:, :-1]], axis=1) for ee, x in zip(e1, inc)))
+    aj = (np.arange(nblk * 1024, dtype=np.int64) * C).reshape(nblk, 256, 4)
+    for i in range(4):
+        s_i = _fa_take(sd, (slice(None), slice(None), i))
+        ck = s_i[0]  # the head run's key: the piece's first key
+        c = corr4[:, :, i] & ((run[3] & 1) != 0) & (run[1] == ck)
+        tot = (run[2] + cs4[:, :, i]).astype(np.float32)
+        pos = aj[:, :, i][c]
+        oi[pos] = ck[c]
+        ov[pos] = tot[c]
+        run = _fa_combine(run, s_i)
+    return oi, ov

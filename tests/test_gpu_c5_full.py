@@ -116,11 +116,12 @@ def test_advanced_c5_adversarial_runs(c5, adv):
     """configs[4] at full size with adversarial uploads: client 0 sending
     one index k = 100,000 times, and all n*k = 10^8 records on one index (one run over
     ~50,000 fold lanes).  One fixed-cost pass, no status; every index within the bound
-    any f32 left fold of its run obeys against the exact (float64) sum — the full-size
+    any f32 left fold of its run obeys, and within the tree-height bound of the streaming
+    fold's geometry (longrun.py), against the exact (float64) sum — the full-size
     property check (the oracle's network at 2^27 per case would take minutes)."""
     import torch
 
-    from longrun import assert_near_exact
+    from longrun import assert_near_exact, fold_geometry, tree_height
 
     from fltee import device as dev
     idx, val = c5
@@ -134,4 +135,31 @@ def test_advanced_c5_adversarial_runs(c5, adv):
     assert dev.status() == 0
     del rec
     torch.cuda.empty_cache()
-    assert_near_exact(out, idx, val, D, N)
+    g = fold_geometry(N, K, D)
+    assert g["path"] == "streaming" and g["Hr"] == 1008 and g["C"] >= g["Hr"], g
+    assert_near_exact(out, idx, val, D, N, h=tree_height(g))
+
+
+def test_advanced_c5_all_one_index_exact():
+    """configs[4] at full size, every record on index 7, val = 1.0 where p % 8 == 0 and 0.0
+    elsewhere (the sum 1.25e7 < 2^24: every association exact, longrun.py): the streaming
+    fold's long-chunk geometry (Hr = 1008, C >= Hr, ~100 patch blocks), which no small shape
+    reaches, against bincount x 1f32/n, bit for bit."""
+    import torch
+
+    from longrun import assert_bits, exact_ref, fold_geometry
+
+    from fltee import device as dev
+    g = fold_geometry(N, K, D)
+    assert g["path"] == "streaming" and g["Hr"] == 1008 and g["C"] >= 1024, g
+    assert g["patch_blocks"] > 64, g
+    val = np.zeros(N * K, np.float32)
+    val[::8] = 1.0
+    assert val.sum(dtype=np.float64) == 1.25e7 < 2 ** 24
+    idx = np.full(N * K, 7, np.uint32)
+    rec = torch.from_numpy(dev.pack_records(idx, val)).cuda()
+    out = dev.aggregate(1, rec, N, K, D).cpu().numpy()
+    assert dev.status() == 0
+    del rec
+    torch.cuda.empty_cache()
+    assert_bits(out, exact_ref(idx, val, D, N))

@@ -149,6 +149,43 @@ def test_group_advanced_long_run_and_k_quirk(enclaves, oracle):
     assert np.array_equal(one0.view(np.uint32), run(enclaves[4], c, 1, enc0, k=0).view(np.uint32))
 
 
+_long_enc = {}
+
+
+@pytest.mark.parametrize("alg,ws", [(1, (1, 2, 4, 8)), (6, (1, 2, 8))])
+@pytest.mark.parametrize("lay", ["all_one_index", "two_adjacent", "boundary"])
+def test_group_long_run_exact(enclaves, oracle, lay, alg, ws):
+    """The integer companion of the test above: n = 16, k = 3000, d = 3000 (M = 2^16) with
+    exactly summable values (tests/longrun.py) through the ECALL on the 1-, 2-, 4- and 8-rank
+    eids (alg 6, batch 5: the 1-, 2- and 8-rank ones) — all_one_index's run spans 6 of the 8
+    ranges, two_adjacent's carry must stop at the key change, `boundary` ends index 2997's
+    run on the last position of the range in front of M / 2 and starts index 2998's (26
+    entries, then 2999's) on the next range's first.  Every eid returns bincount x 1f32/n,
+    bit for bit."""
+    from longrun import assert_bits, boundary_base, exact_ref, exact_values, layout, run_span
+    n, k, d = 16, 3000, 3000
+    M = 1 << (n * k + d - 1).bit_length()
+    assert M == 1 << 16
+    ids = np.arange(900, 900 + n, dtype=np.uint32)
+    idx, val = layout(lay, n, k, d, boundary=M // 2, mid=n + 10), exact_values(n * k)
+    if lay == "all_one_index":
+        s0 = run_span(idx, d, 7)
+        assert (s0[1] - 1) // (M // 8) - s0[0] // (M // 8) + 1 == 6
+    elif lay == "boundary":
+        b = boundary_base(M // 2, n * k, d)
+        s0, s1, s2 = (run_span(idx, d, b + i) for i in range(3))
+        assert s0[1] == M // 2 == s1[0] and s1[1] == s2[0]
+        assert min(s0[1] - s0[0], s1[1] - s1[0], s2[1] - s2[0]) > n + 1
+    if lay not in _long_enc:
+        w = oracle.as_weights(idx, val).reshape(n, k)
+        _long_enc[lay] = oracle.encrypt_clients(ids, [w[i].tobytes() for i in range(n)])
+    c = dict(client_ids=ids, d=d, k=k, n=n, name="long_" + lay)
+    ref = exact_ref(idx, val, d, n)
+    for w in ws:
+        out = run(enclaves[w], c, alg, _long_enc[lay], batch=5 if alg == 6 else None)
+        assert_bits(out, ref)
+
+
 @pytest.mark.parametrize("alg", [1, 2, 4])
 def test_group_ragged_payload(enclaves, oracle, alg):
     """Client slices of 8*k + 3 bytes (lib.rs:305-306 floors bytes and records per

@@ -379,6 +379,68 @@ def test_fold_long_run(dev, m, halo, fold_len):
     assert np.array_equal(gi[fold_len:], idx[fold_len:])
 
 
+def _stream_geometry(m, fold_len, halo):
+    """The streaming fold's sizes for fltee_fold_device(m, fold_len, halo).  The geometry
+    query answers for run_advanced, whose fold with the compaction off is exactly this call
+    — launch_fold over all M = m positions with fold_len = its L (d plays no part there,
+    hence the 0) — so the setting is flipped for the query alone and restored; the asserts
+    below fail if the query ever stops taking that branch."""
+    import ctypes
+    from fltee import _lib as L
+    out = (ctypes.c_uint64 * 8)()
+    try:
+        L.lib().fltee_debug_set_advanced_compaction(0)
+        L.lib().fltee_debug_fold_geometry(m, fold_len, 0, halo, out)
+    finally:
+        L.lib().fltee_debug_set_advanced_compaction(1)
+    assert out[0] == 2 and out[6] == m, list(out)
+    return dict(Hr=int(out[1]), C=int(out[2]), lanes=int(out[3]), depth=int(out[4]),
+                patch_blocks=int(out[5]))
+
+
+@pytest.mark.parametrize("m,halo,fold_len,regime", [
+    (4096, 8, 4096, dict(Hr=16, C=16, depth=2, patch_blocks=1)),
+    # C = 16 < Hr = 112, a partial last wave, an odd lane count, a copied tail
+    ((1 << 16) + 2, 100, 60001, dict(Hr=112, C=16, lanes=4097, depth=2, patch_blocks=5)),
+    (1 << 22, 16, 1 << 22, dict(Hr=16, C=64, depth=1)),
+    (1 << 23, 16, 1 << 23, dict(Hr=16, C=128, depth=1)),  # the doubled chunk
+])
+def test_fold_long_runs_exact(dev, m, halo, fold_len, regime):
+    """fltee_fold_device on pre-sorted runs of 1 to 50,000 entries with small positive
+    integer values (every run's sum exact under any association): the whole of dst equals
+    the enclave's sequential fold bit for bit — every run of the folded part leaves exactly
+    one record (its key, its sum), at its last position when it has <= halo + 1 entries and
+    anywhere inside it otherwise (the patch writes it at a walk's first position), dummies
+    (u32::MAX - p, +0.0) elsewhere, the positions past fold_len copied.  Then N(0, 1) values
+    on the same keys: dst equals tests/range_ops_np.py's fold_stream_model — the lanes'
+    walks, the wave scan, the patch's slices, block scans and run.Q + S — bit for bit."""
+    import torch
+    from longrun import assert_sequential_fold, sorted_runs
+    from range_ops_np import fold_stream_model
+    g = _stream_geometry(m, fold_len, halo)
+    assert {key: g[key] for key in regime} == regime, g
+    idx, B = sorted_runs(m, g["Hr"], g["C"], seed=m)
+    val = (1 + np.arange(m) % 7).astype(np.float32)
+    src = cuda_records(dev, idx, val)
+    dst = torch.empty_like(src)
+    st = torch.zeros(1, dtype=torch.int32, device="cuda")
+    dev.fold(src, dst, fold_len, halo, st)
+    torch.cuda.synchronize()
+    assert int(st.item()) == 0
+    gi, gv = dev.unpack_records(dst.cpu().numpy())
+    assert_sequential_fold(gi, gv, idx, val, fold_len, halo)
+    # (b) N(0, 1) values: the device's own association, bit for bit
+    val = np.random.default_rng(m + 1).normal(0, 1, m).astype(np.float32)
+    src = cuda_records(dev, idx, val)
+    dev.fold(src, dst, fold_len, halo, st)
+    torch.cuda.synchronize()
+    assert int(st.item()) == 0
+    gi, gv = dev.unpack_records(dst.cpu().numpy())
+    mi, mv = fold_stream_model(idx, val, fold_len, halo, g["Hr"], g["C"])
+    di = np.flatnonzero((gi != mi) | (gv.view(np.uint32) != mv.view(np.uint32)))
+    assert di.size == 0, [(int(q), int(gi[q]), float(gv[q]), int(mi[q]), float(mv[q])) for q in di[:8]]
+
+
 # ---------------------------------------------------------- advanced -------
 @pytest.mark.parametrize("n,d,k", [(1, 16, 4), (10, 1000, 100), (100, 50890, 5089), (7, 3333, 1)])
 def test_advanced_bit_exact(dev, oracle, n, d, k):
@@ -666,9 +728,10 @@ def test_advanced_adversarial_runs_c3_shape(dev, oracle, adv, alg, fused):
     index (a run of n*k + 1 = 508,901 entries across every tile and lane), two clients
     splitting theirs over two indices.  Fixed cost, no status: every run of <= n + 1
     entries bit for bit against the oracle's advanced (alg 6: its batches of 30), the long
-    ones within the re-association bound — through the fused fold + compaction (the
-    tiles' look-back carries) and through the streaming fold + patch."""
-    from longrun import assert_advanced
+    ones within the re-association bound and every index within the tree-height bound of
+    the exact sum (longrun.py) — through the fused fold + compaction (the tiles' look-back
+    carries) and through the streaming fold + patch."""
+    from longrun import assert_advanced, fold_geometry, tree_height
 
     from fltee import _lib as L
     n, d, k = 100, 50890, 5089
@@ -691,9 +754,218 @@ def test_advanced_adversarial_runs_c3_shape(dev, oracle, adv, alg, fused):
     try:
         out = dev.aggregate(alg, rec, n, k, d, batch=30 if alg == 6 else 0).cpu().numpy()
         assert dev.status() == 0
+        # the tree-height bound (longrun.py) against the exact sums, from this path's geometry
+        # (alg 6: its batches of 30 and 10 clients, four sums added in order)
+        gs = [fold_geometry(nb, k, d) for nb in ((30, 10) if alg == 6 else (n,))]
+        assert all(g["path"] == ("fused" if fused else "streaming") for g in gs), gs
+        h = max(tree_height(g, batches=4 if alg == 6 else 0) for g in gs)
     finally:
         L.lib().fltee_debug_set_fold_compact(1)
-    assert assert_advanced(out, ref, idx, val, d, n) >= 1
+    assert assert_advanced(out, ref, idx, val, d, n, h=h) >= 1
+    if adv == "all_one_index" and alg == 1:  # the figures DESIGN.md records
+        exact = float(val.astype(np.float64).sum()) / n
+        print(f"\nall_one_index fused={fused} h={h}: |out - exact| = {abs(float(out[7]) - exact):.3e}, "
+              f"|oracle - exact| = {abs(float(ref[7]) - exact):.3e}, exact = {exact:.6e}, "
+              f"sum|v|/n = {float(np.abs(val.astype(np.float64)).sum()) / n:.4e}")
+
+
+# ------------------------------------------- the long-run carries, exactly ----
+# Small positive integer values (longrun.exact_values): every association of a run's sum has
+# the left fold's bits, so any piece dropped, doubled or added to the wrong key shows.
+# name: (n, d, k), the regime with the fold fused into the compaction's first pass
+# (fltee_debug_set_fold_compact(1), the default) and with it apart (0), both asserted through
+# fltee_debug_fold_geometry, and the index the one-index layouts use.
+EXACT_SHAPES = {
+    # configs[2]: the decoupled look-back over ~219 tiles / the CEMIT streaming fold, C < Hr
+    "c3": ((100, 50890, 5089), dict(path="fused", per=6, ntiles=219, lim=101, last=False),
+           dict(path="streaming", Hr=112, C=16, depth=1, patch_blocks=35), 7),
+    # L - d < 512: the fused pass is the compaction's last (FINAL 1; 2 with accumulate);
+    # index 1300's run straddles the tile boundary S = 1537.  (Here and at "two_tiles" every
+    # run lies inside the window of the tile that writes it — a record moves left by less
+    # than 512 — so these two pin the window-local carries, not the look-back.)
+    "final": ((4, 3000, 100), dict(path="fused", per=4, S=1537, ntiles=3, last=True),
+              dict(path="streaming", Hr=16, C=16, depth=2, patch_blocks=1), 1300),
+    "two_tiles": ((10, 1000, 100), dict(path="fused", per=4, ntiles=2, last=False),
+                  dict(path="streaming", Hr=16, C=16, depth=2, patch_blocks=1), 7),
+    "per8": ((100, 50890, 8000), dict(path="fused", per=8, M=1 << 20, ntiles=238, last=False),
+             dict(path="streaming", Hr=112, C=16, depth=1, patch_blocks=52), 7),
+    # more tiles than the resident grid (2 blocks x 256 CUs): blocks loop over tiles, and a
+    # look-back has more than 512 predecessors (a second round is possible)
+    "looped": ((100, 50890, 20000), dict(path="fused", per=8, M=1 << 21, ntiles=573, last=False),
+               dict(path="streaming", Hr=112, C=16, depth=1, patch_blocks=126), 7),
+    # lim = 201 > 128 on more than 2^20 records: the streaming fold by default
+    "lim201": ((200, 50890, 6000), dict(path="streaming", M=1 << 21, Hr=208, C=16, depth=1),
+               dict(path="streaming", M=1 << 21, Hr=208, C=16, depth=1), 7),
+}
+_exact_oracle = {}
+
+
+def _exact_case(dev, shape, lay, fused):
+    """(n, d, k), idx, val and the records on the device for one layout of EXACT_SHAPES[shape],
+    with the regime asserted under the current fold_compact setting"""
+    from longrun import boundary_base, boundary_position, exact_values, fold_geometry, layout, run_span
+    (n, d, k), want1, want0, base = EXACT_SHAPES[shape]
+    g = fold_geometry(n, k, d)
+    want = want1 if fused else want0
+    assert {key: g[key] for key in want} == want, g
+    B = boundary_position(g, n * k)
+    lim = g["lim"] if g["path"] == "fused" else g["Hr"] + 1
+    # (the middle run: longer than a walk and than the halo, inside the unit it starts in; in
+    # the fused pass past the tile's first 511 slots too, so that its record — which the
+    # first levels move left by up to 511 — is one its own tile writes, the only place a
+    # look-back carry can land)
+    mid = max(lim, g["Hr"] + 1) + 9
+    if g["path"] == "fused":
+        mid = max(mid, min(g["Hr"] + 600, n * k // 4))
+    idx = layout(lay, n, k, d, boundary=B, base=base, mid=mid)
+    val = exact_values(n * k)
+    if lay == "boundary":
+        b = boundary_base(B, n * k, d)
+        s0, s1, s2 = (run_span(idx, d, b + i) for i in range(3))
+        assert s0[1] == B == s1[0] and s1[1] - s1[0] == mid > lim and s1[1] == s2[0], (s0, s1, s2, B)
+        assert s0[1] - s0[0] > lim and s2[1] - s2[0] > lim
+    elif lay == "all_one_index":
+        s0 = run_span(idx, d, base)
+        assert s0[1] - s0[0] == n * k + 1 > lim
+        if shape == "final":
+            assert s0[0] < g.get("S", 1537) < s0[1]
+    return (n, d, k), idx, val, cuda_records(dev, idx, val)
+
+
+@pytest.mark.parametrize("fused", [1, 0])
+@pytest.mark.parametrize("lay", ["one_client", "all_one_index", "two_adjacent", "index_zero",
+                                 "last_and_beyond", "boundary"])
+@pytest.mark.parametrize("shape", list(EXACT_SHAPES))
+def test_advanced_long_run_exact(dev, oracle, shape, lay, fused):
+    """`advanced` on the adversarial layouts with exactly summable values == the per-index
+    sums (bincount) x 1f32/n, bit for bit, through the fused fold's look-back and through the
+    streaming fold + patch; at configs[2]'s shape also the oracle's bits."""
+    from longrun import assert_bits, exact_ref
+    from fltee import _lib as L
+    L.lib().fltee_debug_set_fold_compact(fused)
+    try:
+        (n, d, k), idx, val, rec = _exact_case(dev, shape, lay, fused)
+        out = dev.aggregate(1, rec, n, k, d).cpu().numpy()
+        assert dev.status() == 0
+    finally:
+        L.lib().fltee_debug_set_fold_compact(1)
+    assert_bits(out, exact_ref(idx, val, d, n))
+    if shape == "c3":
+        key = (lay, idx.tobytes() if lay == "boundary" else None)
+        if key not in _exact_oracle:
+            _exact_oracle[key] = oracle.advanced(k, oracle.as_weights(idx, val), d, n)
+        ref, rst = _exact_oracle[key]
+        assert rst == 0
+        assert_bits(out, ref)
+
+
+@pytest.mark.parametrize("fused", [1, 0])
+@pytest.mark.parametrize("lay", ["one_client", "all_one_index", "two_adjacent", "index_zero",
+                                 "last_and_beyond", "boundary"])
+def test_advanced_long_run_exact_accumulate(dev, lay, fused):
+    """The same onto a random `prev` (accumulate: the fused last pass's FINAL 2 adds the run
+    sums, no 1/n): prev + sums, one f32 addition an index on both sides."""
+    import torch
+    from longrun import assert_bits, exact_ref
+    from fltee import _lib as L
+    L.lib().fltee_debug_set_fold_compact(fused)
+    try:
+        (n, d, k), idx, val, rec = _exact_case(dev, "final", lay, fused)
+        prev = np.random.default_rng(9).normal(0, 100, d).astype(np.float32)
+        acc = torch.from_numpy(prev.copy()).cuda()
+        dev.aggregate(1, rec, n, k, d, out=acc, accumulate=True)
+        assert dev.status() == 0
+    finally:
+        L.lib().fltee_debug_set_fold_compact(1)
+    assert_bits(acc.cpu().numpy(), prev + exact_ref(idx, val, d, 1))
+
+
+@pytest.mark.parametrize("fused", [1, 0])
+@pytest.mark.parametrize("lay", ["all_one_index", "one_client"])
+@pytest.mark.parametrize("n,d,k,batch", [(100, 50890, 5089, 30), (10, 2000, 150, 1),
+                                         (10, 2000, 150, 3), (10, 2000, 150, 10)])
+def test_optimized_alg6_long_run_exact(dev, n, d, k, batch, lay, fused):
+    """alg 6: every batch's `advanced` carries its own long run (halo = the batch's clients),
+    the batch sums add up exactly too: bincount x 1f32/n, bit for bit."""
+    from longrun import assert_bits, exact_ref, exact_values, fold_geometry, layout
+    from fltee import _lib as L
+    idx, val = layout(lay, n, k, d), exact_values(n * k)
+    rec = cuda_records(dev, idx, val)
+    L.lib().fltee_debug_set_fold_compact(fused)
+    try:
+        for nb in {min(batch, n), n % batch or batch}:  # the batch sizes alg 6 folds
+            g = fold_geometry(nb, k, d)
+            assert g["path"] == ("fused" if fused else "streaming"), g
+            # k + 1 entries are beyond every batch's walk: all_one_index has such a run (of
+            # nb k + 1) in every batch, one_client in the batch that holds client 0
+            assert k + 1 > (g["lim"] if fused else g["Hr"] + 1), g
+        out = dev.aggregate(6, rec, n, k, d, batch=batch).cpu().numpy()
+        assert dev.status() == 0
+    finally:
+        L.lib().fltee_debug_set_fold_compact(1)
+    assert_bits(out, exact_ref(idx, val, d, n))
+
+
+def test_advanced_k0_quirk_long_run_exact(dev, oracle):
+    """The k quirk (k_req = 0: only the first d sorted positions folded, the enclave's second
+    sort instead of the compaction) with every record on index 7 and the default halo: the
+    run over [7, d) is cut at fold_len and finished by the streaming fold's patch, which
+    writes its one record at a walk's first position a (a multiple of C) instead of the run's
+    last.  The second network then orders the unfolded index-7 records and that record by
+    where they start, so the reference is the oracle's own networks and fold with that one
+    record moved to a — bit for bit, on exactly summable values.  That placement is a
+    modelled implementation detail of the patch (k_fold.hip: dst[a_j] of the lane the run
+    ends in), not a property of `advanced`: on this point the reference follows the device,
+    and a change of the placement rule has to change it here too.  What it pins
+    independently is the record's sum (the whole cut run's, exact) and that nothing else in
+    the folded array moved; where k_req = k the output does not depend on the placement and
+    the tests above compare per-index sums alone."""
+    from longrun import assert_bits, exact_values, fold_geometry, layout
+    from fltee import _lib as L
+    n, d = 5, 300
+    idx, val = layout("all_one_index", n, d, d), exact_values(n * d)
+    try:
+        L.lib().fltee_debug_set_advanced_compaction(0)  # the quirk's fold covers all M
+        g = fold_geometry(n, d, d)
+    finally:
+        L.lib().fltee_debug_set_advanced_compaction(1)
+    assert g["path"] == "streaming" and g["span"] == g["M"] and d - 7 > g["Hr"] + 1, g
+    rec = cuda_records(dev, idx, val)
+    out = dev.aggregate(1, rec, n, d, d, k_req=0).cpu().numpy()
+    assert dev.status() == 0
+    M, pad = g["M"], g["M"] - g["L"]
+    w = np.concatenate([oracle.as_weights(idx, val),
+                        oracle.as_weights(np.arange(d, dtype=np.uint32), np.zeros(d, np.float32)),
+                        oracle.as_weights(np.full(pad, U32MAX, np.uint32), np.zeros(pad, np.float32))])
+    f = oracle.fold(oracle.bitonic_sort(w), d)
+    a = (d - 1) // g["C"] * g["C"]
+    assert f["idx"][d - 1] == 7 and f["idx"][a] == U32MAX - a
+    f["idx"][a], f["val"][a] = 7, f["val"][d - 1]
+    f["idx"][d - 1], f["val"][d - 1] = U32MAX - (d - 1), 0.0
+    ref = oracle.bitonic_sort(f)["val"][:d] * (np.float32(1) / np.float32(n))
+    assert len(f) == M
+    assert_bits(out, ref)
+
+
+@pytest.mark.parametrize("fused", [1, 0])
+def test_advanced_long_run_no_stale_carry(dev, fused):
+    """all_one_index and then index_zero at the same shape, back to back on one context: a
+    look-back slot of the launch before (the epoch) or a stale side record would leak index
+    7's partials into index 0's."""
+    from longrun import assert_bits, exact_ref
+    from fltee import _lib as L
+    L.lib().fltee_debug_set_fold_compact(fused)
+    try:
+        outs = []
+        for lay in ("all_one_index", "index_zero", "all_one_index"):
+            (n, d, k), idx, val, rec = _exact_case(dev, "c3", lay, fused)
+            out = dev.aggregate(1, rec, n, k, d)
+            outs.append((out, exact_ref(idx, val, d, n)))
+        assert dev.status() == 0
+    finally:
+        L.lib().fltee_debug_set_fold_compact(1)
+    for out, ref in outs:
+        assert_bits(out.cpu().numpy(), ref)
 
 
 @pytest.mark.parametrize("n,d,k", [(10, 4000, 1000), (10, 8000, 1000), (10, 16000, 1000),

@@ -112,6 +112,36 @@ def test_index_sharded_advanced_bit_exact(dev, oracle, world, n, d, k, idx_hi, e
     assert (nlong > 0) == (idx_hi == 64)
 
 
+@pytest.mark.parametrize("exchange", ["transpose", "pairwise"])
+@pytest.mark.parametrize("lay", ["one_client", "all_one_index", "two_adjacent", "index_zero",
+                                 "last_and_beyond", "boundary"])
+@pytest.mark.parametrize("world", [2, 4, 8])
+def test_index_sharded_advanced_long_run_exact(dev, world, lay, exchange):
+    """The long-run layouts (tests/longrun.py) on exactly summable values through the range
+    folds, the ranges' totals and the patches: bincount x 1f32/n, bit for bit.  n = 20,
+    d = 3000, k = 400 (M = 2^14); `boundary` ends index 2997's run on the last position of
+    the range in front of M / 2 and starts index 2998's (30 entries, then 2999's) on the next
+    range's first."""
+    import torch
+
+    from longrun import assert_bits, boundary_base, exact_ref, exact_values, layout, run_span
+
+    from fltee.parallel import VirtualRanks, index_sharded_advanced
+    n, d, k = 20, 3000, 400
+    M = 1 << (n * k + d - 1).bit_length()
+    idx, val = layout(lay, n, k, d, boundary=M // 2, mid=n + 10), exact_values(n * k)
+    if lay == "boundary":
+        b = boundary_base(M // 2, n * k, d)
+        s0, s1, s2 = (run_span(idx, d, b + i) for i in range(3))
+        assert s0[1] == M // 2 == s1[0] and s1[1] == s2[0]
+        assert min(s0[1] - s0[0], s1[1] - s1[0], s2[1] - s2[0]) > n + 1
+        assert (M // 2) % (M // world) == 0
+    rec = torch.from_numpy(dev.pack_records(idx, val)).cuda()
+    out = index_sharded_advanced(init_chunks(dev, rec, n * k, d, world, M), world, M, n, k, d,
+                                 comm=VirtualRanks(world), exchange=exchange)
+    assert_bits(out.cpu().numpy(), exact_ref(idx, val, d, n))
+
+
 def test_index_sharded_matches_single_gpu_at_scale(dev):
     """configs[2]-like shape at 2^21: sharded x4 == fltee_aggregate_device(advanced)."""
     import torch

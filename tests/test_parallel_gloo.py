@@ -115,7 +115,16 @@ def case_b():
     return n, d, k, idx, val
 
 
-def worker_b(rank, world, port, outdir, exchange):
+def case_b_long(lay):
+    """the long-run layouts on exactly summable values (tests/longrun.py), at
+    test_sharded_model.py's shape"""
+    from longrun import exact_values, layout
+    n, d, k = 6, 400, 100
+    M = 1 << (n * k + d - 1).bit_length()
+    return n, d, k, layout(lay, n, k, d, boundary=M // 2, mid=n + 10), exact_values(n * k)
+
+
+def worker_b(rank, world, port, outdir, exchange, lay=None):
     import sys
     for p in (ROOT, os.path.join(ROOT, "fl-tee_amd"), os.path.join(ROOT, "oracle"),
               os.path.join(ROOT, "tests")):
@@ -125,7 +134,7 @@ def worker_b(rank, world, port, outdir, exchange):
     from fltee import parallel as P
     dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank,
                             world_size=world)
-    n, d, k, idx, val = case_b()
+    n, d, k, idx, val = case_b_long(lay) if lay else case_b()
     M = 1 << (n * k + d - 1).bit_length()
     C = M // world
     chunks = {rank: init_range(idx, val, d, rank * C, C)}
@@ -148,6 +157,18 @@ def test_index_sharded_advanced_gloo(oracle, tmp_path, world, exchange):
     assert st == 0
     got = np.load(tmp_path / "adv_b.npy")
     assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+
+
+@pytest.mark.parametrize("lay", ["all_one_index", "two_adjacent", "boundary"])
+@pytest.mark.parametrize("exchange,world", [("transpose", 4), ("pairwise", 2)])
+def test_index_sharded_advanced_long_run_exact_gloo(tmp_path, world, exchange, lay):
+    """Long runs across the ranges over gloo (DistRanks: the totals really travel): the
+    per-index sums x 1f32/n bit for bit on exactly summable values."""
+    from longrun import assert_bits, exact_ref
+    mp.spawn(worker_b, args=(world, free_port(), str(tmp_path), exchange, lay), nprocs=world,
+             join=True)
+    n, d, k, idx, val = case_b_long(lay)
+    assert_bits(np.load(tmp_path / "adv_b.npy"), exact_ref(idx, val, d, n))
 
 
 # ---- position-range sharded nips19: DistRanks.gather_lists over gloo ----
