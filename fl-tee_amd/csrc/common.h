@@ -199,6 +199,16 @@ hipError_t bitonic_exchange(uint64_t *mine, const uint64_t *theirs, size_t m, ui
                             uint32_t pos_theirs, uint32_t mode, uint32_t seed, uint32_t ilog,
                             uint32_t jlog, hipStream_t s);
 
+// k_stable.hip: alg 7's stable network on 16-byte records {u64 key = idx << 32 | position;
+// f32 val; u32 pad}, in place on data16[0, m), m = 2^j <= stable_sort_max_records().
+// valid (0: unknown): positions >= valid hold identical pads (key ~0, +0.0); init: the
+// entries are built from rec[0, nrec) ++ (i, +0.0), i < d, ++ pads on the way in; out8: the
+// sorted array leaves as the fold's 8-byte (idx, val) records there (data16 is scratch).
+size_t stable_sort_max_records();
+hipError_t stable_sort(void *data16, size_t m, hipStream_t s, size_t valid = 0, bool init = false,
+                       const void *rec = nullptr, size_t nrec = 0, size_t d = 0,
+                       uint64_t *out8 = nullptr);
+
 // k_fold.hip
 hipError_t launch_advanced_init(const void *rec, size_t nrec, size_t d, size_t m, uint64_t *dst,
                                 hipStream_t s);

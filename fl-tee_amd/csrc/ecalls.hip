@@ -490,16 +490,24 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     if (uint32_t st = check_uploaded(cfg, client_ids, n)) return fail(st);
     for (size_t i = 0; i < n; ++i)
         if (!g_keys.count(client_ids[i])) return fail(FLTEE_ERROR_UNEXPECTED);  // lib.rs:319-322
-    switch (aggregation_alg) {  // lib.rs:359-397 (6 and 7 are not dispatched here: panic)
+    // lib.rs:359-397: 6 is not dispatched here (panic); 7 is bubble_sort_based (lib.rs:389),
+    // answered by the stable network (k_stable.hip) with the enclave's in-order result once
+    // the host has opted in (fltee_set_bubble_ecall(1)); until then it stays the 0x2 that
+    // hosts of earlier versions get for it
+    switch (aggregation_alg) {
     case FLTEE_ALG_ADVANCED: case FLTEE_ALG_NIPS19: case FLTEE_ALG_BASELINE:
     case FLTEE_ALG_NON_OBLIVIOUS: case FLTEE_ALG_PATH_ORAM: break;
+    case FLTEE_ALG_BUBBLE:
+        if (bubble_ecall_default()) break;
+        [[fallthrough]];
     default: return fail(FLTEE_ERROR_INVALID_PARAMETER);
     }
     // lib.rs:305-306: bytes per client floored, records per client floored; slice i
     // starts at i*bpc even when that is not a record boundary (ragged payloads)
     const size_t bpc = encrypted_parameters_size / n;
     const size_t rpc = bpc / 8;
-    if (aggregation_alg == FLTEE_ALG_ADVANCED && n * num_of_sparse_parameters > n * rpc)
+    if ((aggregation_alg == FLTEE_ALG_ADVANCED || aggregation_alg == FLTEE_ALG_BUBBLE) &&
+        n * num_of_sparse_parameters > n * rpc)
         return fail(FLTEE_ERROR_INVALID_PARAMETER);  // advanced.rs:72 out-of-bounds panic
 
     if (!c->outbuf.reserve(d * 4 + 16)) return fail(FLTEE_ERROR_OUT_OF_MEMORY);

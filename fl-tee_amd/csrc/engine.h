@@ -42,6 +42,7 @@ struct DeviceCtx {
     Buffer ws_oram;            // path_oram tree mode: the tree + stash slots, then their records
     Buffer ws_side;            // advanced's streaming fold: its side records (k_fold.hip)
     Buffer ws_lb;              // the fused fold's look-back slots (k_compact.hip), zeroed
+    Buffer ws_s16;             // alg 7: the stable network's 16-byte records (k_stable.hip)
     uint32_t fc_epoch = 0;     // their launch counter
     uint32_t *host_word = nullptr;                       // pinned readback word
     hipStream_t stream = nullptr;                        // ECALL stream
@@ -68,6 +69,10 @@ bool oram_tree_default();
 // else the halo fold (bit for bit up to n + 1 entries a run, re-associated beyond)
 void set_exact_runs(int on);
 bool exact_runs_default();
+// alg 7 (lib.rs:389) through ecall_secure_aggregation: answered only after
+// fltee_set_bubble_ecall(1); off (default) it stays the 0x2 it has always been
+void set_bubble_ecall(int on);
+bool bubble_ecall_default();
 
 fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size_t d, float *out,
                          const fltee_device_opts &o, hipStream_t s, uint32_t *status);

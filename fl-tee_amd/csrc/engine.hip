@@ -184,6 +184,7 @@ struct Plan {
     size_t side_bytes = 0;                   // advanced's streaming fold: side records
     size_t lb_bytes = 0;                     // advanced's fused fold: look-back slots
     size_t oram_bytes = 0;                   // path_oram tree: slots (16 B) + their records (8 B)
+    size_t s16_bytes = 0;                    // alg 7: the stable network's 16-byte records
 };
 
 // the side records of advanced's streaming fold over its array (M) or its compaction
@@ -230,6 +231,9 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
             else p.keys_bytes = n * k * 8, p.radix_bytes = radix_scratch_bytes(n * k, d);
         }
         break;
+    case FLTEE_ALG_BUBBLE:  // advanced's arrays behind the stable network's own
+        p.s16_bytes = next_pow2_sz(n * k + d) * 16;
+        [[fallthrough]];
     case FLTEE_ALG_ADVANCED:
         p.a_bytes = p.b_bytes = next_pow2_sz(n * k + d) * 8;
         p.side_bytes = advanced_side_bytes(n, k, d, o.fold_halo ? o.fold_halo : n);
@@ -269,7 +273,7 @@ static bool reserve_plan(DeviceCtx *c, const Plan &p) {
            c->ws_coef.reserve(p.coef_bytes) && c->ws_rec.reserve(p.rec_bytes) &&
            c->ws_keys.reserve(p.keys_bytes) && c->ws_radix.reserve(p.radix_bytes) &&
            c->ws_oram.reserve(p.oram_bytes) && c->ws_side.reserve(p.side_bytes) &&
-           reserve_lb(c, p.lb_bytes);
+           c->ws_s16.reserve(p.s16_bytes) && reserve_lb(c, p.lb_bytes);
 }
 
 // The ordered fold of n records (common.rs:25-35, non_oblivious.rs:11-13): the records in
@@ -283,6 +287,9 @@ void set_radix_order(int on) { g_radix_order = on != 0; }
 static bool g_exact_runs = false;  // the ECALLs' advanced / alg 6: reject runs > n + 1 unless set
 void set_exact_runs(int on) { g_exact_runs = on != 0; }
 bool exact_runs_default() { return g_exact_runs; }
+static bool g_bubble_ecall = false;  // ecall_secure_aggregation answers alg 7 only when set
+void set_bubble_ecall(int on) { g_bubble_ecall = on != 0; }
+bool bubble_ecall_default() { return g_bubble_ecall; }
 static bool g_oram_tree = false;  // the ECALLs' path_oram: the sweep unless set
 void set_oram_tree(int on) { g_oram_tree = on != 0; }
 bool oram_tree_default() { return g_oram_tree; }
@@ -387,16 +394,23 @@ static size_t advanced_fold_span(size_t L, size_t M) {
     return mf > M ? M : mf;
 }
 
+// stable: alg 7 — the array is sorted by (idx, upload position) through the stable
+// network (k_stable.hip) instead of advanced's first sort; everything after it is shared.
 static hipError_t run_advanced(DeviceCtx *c, const void *rec, size_t n, size_t k, size_t d,
                                size_t k_req, size_t halo, float coef, float *out, bool acc,
-                               uint32_t *status, hipStream_t s) {
+                               uint32_t *status, hipStream_t s, bool stable = false) {
     const size_t L = n * k + d, M = next_pow2_sz(L);
     const size_t fold_len = n * k_req + d;
     uint64_t *A = (uint64_t *)c->ws_a.ptr, *B = (uint64_t *)c->ws_b.ptr;
-    hipError_t e = bitonic_sort_advanced(A, M, rec, n * k, d, s);  // init fused into the sort
-    if (e == hipErrorNotSupported) {
-        e = launch_advanced_init(rec, n * k, d, M, A, s);
-        if (e == hipSuccess) e = bitonic_sort(A, M, 0, 0, s, L);
+    hipError_t e;
+    if (stable) {  // init fused into the first pass, strip into the last
+        e = stable_sort(c->ws_s16.ptr, M, s, L, true, rec, n * k, d, A);
+    } else {
+        e = bitonic_sort_advanced(A, M, rec, n * k, d, s);  // init fused into the sort
+        if (e == hipErrorNotSupported) {
+            e = launch_advanced_init(rec, n * k, d, M, A, s);
+            if (e == hipSuccess) e = bitonic_sort(A, M, 0, 0, s, L);
+        }
     }
     if (e != hipSuccess) return e;
     // Second sort (advanced.rs:106-111): with fold_len == L its [0, d) prefix is the
@@ -462,6 +476,12 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     // the networks address records with 32-bit byte offsets: arrays of <= 2^29 records
     // (k_bitonic.hip, k_compact.hip); refuse larger ones before reserving scratch
     constexpr size_t kMaxNet = (size_t)1 << 29;
+    if (alg == FLTEE_ALG_BUBBLE) {
+        // bubble_sort_based.rs:42 folds n * k_req + d entries; only k_req == k is answered
+        if ((o.flags & FLTEE_OPT_K_REQ) && o.k_req != k) return FLTEE_ERROR_INVALID_PARAMETER;
+        if (next_pow2_sz(n * k + d) > kMaxNet || next_pow2_sz(n * k + d) > stable_sort_max_records())
+            return FLTEE_ERROR_INVALID_PARAMETER;
+    }
     if ((alg == FLTEE_ALG_ADVANCED && next_pow2_sz(n * k + d) > kMaxNet) ||
         (alg == FLTEE_ALG_OPTIMIZED &&
          next_pow2_sz((o.batch && o.batch < n ? o.batch : n) * k + d) > kMaxNet) ||
@@ -561,6 +581,9 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
         e = run_advanced(c, rec, n, k, d, k_req, o.fold_halo, coef, out, acc, status, s);
         break;
     }
+    case FLTEE_ALG_BUBBLE:  // the stable sort, then advanced's fold / compaction / extract
+        e = run_advanced(c, rec, n, k, d, k, o.fold_halo, coef, out, acc, status, s, true);
+        break;
     case FLTEE_ALG_OPTIMIZED: {
         const size_t batch = o.batch ? o.batch : n;
         if (!acc) e = fl_memset_async(out, 0, d * 4, s);
@@ -618,7 +641,7 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
 size_t workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
     const Plan p = plan_for(alg, n, k, d, o);
     return p.a_bytes + p.b_bytes + p.mat_bytes + p.r_bytes + p.coef_bytes + p.rec_bytes +
-           p.keys_bytes + p.radix_bytes + p.oram_bytes + p.side_bytes + p.lb_bytes;
+           p.keys_bytes + p.radix_bytes + p.oram_bytes + p.side_bytes + p.lb_bytes + p.s16_bytes;
 }
 
 bool reserve(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
@@ -682,6 +705,12 @@ extern "C" fltee_status_t fltee_bitonic_device(void *d_records, size_t m, uint32
     return bitonic_sort((uint64_t *)d_records, m, mode, seed, (hipStream_t)stream) == hipSuccess
                ? FLTEE_SUCCESS
                : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_stable_sort_device(void *d_records16, size_t m, void *stream) {
+    if (m == 0 || (m & (m - 1)) || m > stable_sort_max_records()) return FLTEE_ERROR_INVALID_PARAMETER;
+    return stable_sort(d_records16, m, (hipStream_t)stream) == hipSuccess ? FLTEE_SUCCESS
+                                                                          : FLTEE_ERROR_UNEXPECTED;
 }
 
 extern "C" fltee_status_t fltee_fold_device(const void *d_src, void *d_dst, size_t m,
@@ -1043,6 +1072,10 @@ extern "C" void fltee_set_path_oram_tree(int on) {
 extern "C" void fltee_set_advanced_exact_runs(int on) {
     std::lock_guard<std::recursive_mutex> lk(fltee::api_mutex());
     fltee::set_exact_runs(on);
+}
+extern "C" void fltee_set_bubble_ecall(int on) {
+    std::lock_guard<std::recursive_mutex> lk(fltee::api_mutex());
+    fltee::set_bubble_ecall(on);
 }
 // test hook: blocks a bucket of the tree ORAM takes on eviction (4; 0 forces the stash)
 extern "C" void fltee_debug_set_oram_bucket(int z) {

@@ -19,6 +19,7 @@ ERROR_OUT_OF_MEMORY = 0x3
 ERROR_INVALID_ENCLAVE_ID = 0x2002
 
 ALG_ADVANCED, ALG_NIPS19, ALG_BASELINE, ALG_NON_OBLIVIOUS, ALG_PATH_ORAM, ALG_OPTIMIZED = 1, 2, 3, 4, 5, 6
+ALG_BUBBLE = 7  # lib.rs:389 (the reference bench's `-a bubble`; not in option.py, not in ALG_CODES)
 ALG_CODES = {  # src/option.py:131-145
     "advanced": ALG_ADVANCED, "nips19": ALG_NIPS19, "baseline": ALG_BASELINE,
     "non_oblivious": ALG_NON_OBLIVIOUS, "path_oram": ALG_PATH_ORAM, "optimized": ALG_OPTIMIZED,
@@ -72,6 +73,7 @@ SIGNATURES = {
     "fltee_sum_rows_device": (_U32, [_P, _S, _S, _F, _P, _P]),
     "fltee_dp_noise_device": (_U32, [_P, _S, _F, _F, _S, _U64, _P]),
     "fltee_bitonic_device": (_U32, [_P, _S, _U32, _U32, _P]),
+    "fltee_stable_sort_device": (_U32, [_P, _S, _P]),
     "fltee_fold_device": (_U32, [_P, _P, _S, _S, _S, _P, _P]),
     "fltee_laplace_r_device": (_U32, [_S, _S, _S, _U64, _P, _P, _P]),
     "fltee_client_topk_device": (_U32, [_P, _S, _S, _S, _P, _P]),
@@ -97,6 +99,7 @@ SIGNATURES = {
     "fltee_debug_set_seed": (None, [_U64]),
     "fltee_set_path_oram_tree": (None, [ctypes.c_int]),
     "fltee_set_advanced_exact_runs": (None, [ctypes.c_int]),
+    "fltee_set_bubble_ecall": (None, [ctypes.c_int]),
     "fltee_version": (ctypes.c_char_p, []),
     "fltee_device_init_multi": (_U32, [_P, ctypes.c_int, _P]),
     "fltee_device_count": (ctypes.c_int, [_U64]),

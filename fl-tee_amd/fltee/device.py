@@ -93,6 +93,16 @@ def bitonic(records, mode, seed=0, stream=None):
     return records
 
 
+def stable_sort(records16, stream=None):
+    """fltee_stable_sort_device: alg 7's network in place on 16-byte records {u64 key; f32
+    val; u32 pad} (any tensor whose bytes are m = 2^j such records), ascending by key."""
+    nbytes = records16.numel() * records16.element_size()
+    assert records16.is_cuda and records16.is_contiguous() and nbytes % 16 == 0
+    _check(L.lib().fltee_stable_sort_device(_ptr(records16), nbytes // 16, _stream(stream)),
+           "fltee_stable_sort_device")
+    return records16
+
+
 def fold(src, dst, fold_len, halo, status_word, stream=None):
     _check(L.lib().fltee_fold_device(_ptr(src), _ptr(dst), src.numel(), fold_len, halo,
                                      _ptr(status_word), _stream(stream)), "fltee_fold_device")

@@ -116,6 +116,13 @@ def set_path_oram_tree(on):
     L.lib().fltee_set_path_oram_tree(1 if on else 0)
 
 
+def set_bubble_ecall(on):
+    """aggregation_alg 7 (lib.rs:389) through ecall_secure_aggregation: refused with 0x2 when
+    off (default), answered with the enclave's in-order result when on
+    (fltee_set_bubble_ecall)."""
+    L.lib().fltee_set_bubble_ecall(1 if on else 0)
+
+
 def set_advanced_exact_runs(on):
     """aggregation_alg 1 and 6 through the ECALLs when some index has a run of more than
     n + 1 entries (a client repeated an index): off (default) answers at the fixed cost of

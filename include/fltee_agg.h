@@ -62,6 +62,24 @@ typedef uint64_t fltee_eid_t;
 #define FLTEE_ALG_NON_OBLIVIOUS 4u
 #define FLTEE_ALG_PATH_ORAM 5u
 #define FLTEE_ALG_OPTIMIZED 6u
+/* lib.rs:389 -> bubble_sort_based.rs (the reference bench's `-a bubble`): records ++ (i, 0.0)
+ * for i < d sorted STABLY by idx, advanced's fold, a second sort, the first d values.  Each
+ * index's run reaches the fold in upload order with its zero entry last, so the result is
+ * the in-order client sum ((v1 + v2) + ... + vc) + 0.0 — the bits of non_oblivious and
+ * baseline — out of an oblivious sort-based pipeline.  Here the O(L^2) bubble passes are
+ * replaced by a data-independent bitonic network on 16-byte records keyed (idx << 32 |
+ * upload position) (k_stable.hip): the same output at O(L log^2 L) fixed cost; the fold,
+ * compaction and extract are advanced's.
+ *   - fold length: n * k_req + d (bubble_sort_based.rs:42); only k_req == k is answered,
+ *     anything else (FLTEE_OPT_K_REQ with another k_req) is FLTEE_ERROR_INVALID_PARAMETER;
+ *   - opts.fold_halo as for advanced: runs of <= halo + 1 entries bit for bit, longer
+ *     ones re-associated at the fold's walk boundaries;
+ *   - records with idx >= d are ignored (they sort behind the d zero entries);
+ *   - size limit: next_pow2(n * k + d) <= 2^29 records (the network holds 16 B per record,
+ *     addressed with 64-bit byte offsets; positions are 32-bit), else INVALID_PARAMETER
+ *     before any scratch is reserved;
+ *   - FLTEE_OPT_CLIP / _DP / _ACCUMULATE / _NO_AVERAGE and n_avg as for advanced. */
+#define FLTEE_ALG_BUBBLE 7u
 
 /* ------------------------------------------------------------------------ */
 /* Device lifetime — replaces init_enclave() / SgxEnclave::destroy()         */
@@ -239,6 +257,10 @@ fltee_status_t fltee_device_status(void *stream, uint32_t *status);
  * mode 2: keyed shuffle network (nips19.rs:66-105 structure, seed)          */
 fltee_status_t fltee_bitonic_device(void *d_records, size_t m, uint32_t mode, uint32_t seed,
                                     void *stream);
+/* In-place stable oblivious network of alg 7 on m = 2^j (<= 2^29) 16-byte records
+ * {u64 key; f32 val; u32 pad}: ascending by key alone (keys distinct, except identical
+ * pads key = ~0, val = +0.0).  Any other m: FLTEE_ERROR_INVALID_PARAMETER. */
+fltee_status_t fltee_stable_sort_device(void *d_records16, size_t m, void *stream);
 /* advanced.rs:66-101 fold over [0, fold_len) of src (length m) into dst. */
 fltee_status_t fltee_fold_device(const void *d_src, void *d_dst, size_t m, size_t fold_len,
                                  size_t halo, uint32_t *d_status, void *stream);
@@ -359,6 +381,13 @@ void fltee_set_path_oram_tree(int on);
  * bit); on = the enclave's exact fold for ANY run length (advanced.rs:66-101), at the
  * public worst-case cost: one sequential walk of the whole sorted array whatever the data. */
 void fltee_set_advanced_exact_runs(int on);
+/* ecall_secure_aggregation with aggregation_alg 7 (lib.rs:389, FLTEE_ALG_BUBBLE): off
+ * (default) = refused with 0x2, as every earlier version of this library did; on = answered
+ * with the enclave's in-order result (the staged and the pipelined path, DP, the round
+ * counter; on an eid over several GPUs it runs on the root).  A host that sends alg 7
+ * switches it on once at start-up.  The device API (fltee_aggregate_device) answers alg 7
+ * whatever this says. */
+void fltee_set_bubble_ecall(int on);
 void fltee_debug_set_seed(uint64_t seed);
 /* Library build/version string. */
 const char *fltee_version(void);
