@@ -73,6 +73,9 @@ static inline size_t next_pow2_sz(size_t x) {
     while (p < x) p <<= 1;
     return p;
 }
+// The networks address their records with 32-bit byte offsets (k_bitonic.hip,
+// k_compact.hip, k_stable.hip): no array any of them runs over holds more records.
+constexpr size_t kMaxNetRecords = (size_t)1 << 29;
 static inline uint32_t log2_pow2(size_t x) {
     uint32_t l = 0;
     while (((size_t)1 << l) < x) ++l;

@@ -166,6 +166,12 @@ static uint32_t read_status(DeviceCtx *c, uint32_t *st) {
     return FLTEE_SUCCESS;
 }
 
+// This ECALL's path_oram takes the tree Path ORAM (fltee_set_path_oram_tree; a shape past
+// the tree's bounds, which aggregate() would refuse, takes the sweep)
+static bool ecall_takes_tree(uint32_t alg, size_t n, size_t rpc, size_t d) {
+    return alg == FLTEE_ALG_PATH_ORAM && oram_tree_default() && oram_fits(n * rpc, d, false);
+}
+
 // The options aggregate_records gives aggregate() for an ECALL's alg (shared with the
 // staged path below).
 static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d, size_t k_req,
@@ -178,8 +184,7 @@ static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d
     const bool flat = alg == FLTEE_ALG_BASELINE || alg == FLTEE_ALG_PATH_ORAM ||
                       alg == FLTEE_ALG_NON_OBLIVIOUS;
     if (flat && rpc == d) o.flags |= FLTEE_OPT_DENSE;
-    if (alg == FLTEE_ALG_PATH_ORAM && oram_tree_default() && oram_fits(n * rpc, d, false))
-        o.flags |= FLTEE_OPT_ORAM_TREE;  // (a shape past the tree's bounds takes the sweep)
+    if (ecall_takes_tree(alg, n, rpc, d)) o.flags |= FLTEE_OPT_ORAM_TREE;
     if (alg == FLTEE_ALG_NIPS19) o.seed = seed ? seed : next_seed();
     // advanced's fold (advanced.rs:66-101) runs once with halo = n: bit for bit for every
     // run of up to n + 1 entries — every upload whose clients each send distinct indices
@@ -519,8 +524,7 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     double t2 = 0;
     const bool flat = aggregation_alg == FLTEE_ALG_BASELINE || aggregation_alg == FLTEE_ALG_PATH_ORAM ||
                       aggregation_alg == FLTEE_ALG_NON_OBLIVIOUS;
-    const bool tree = aggregation_alg == FLTEE_ALG_PATH_ORAM && oram_tree_default() &&
-                      oram_fits(n * rpc, d, false);
+    const bool tree = ecall_takes_tree(aggregation_alg, n, rpc, d);
     if (G && flat && !tree && rpc == d && bpc == d * 8) {
         // dense uploads over a multi-GPU eid: every GPU loads and decrypts its own
         // parameter range (group.hip); "Loading" = the parallel H2D, "Decryption" = the

@@ -11,6 +11,7 @@ constexpr int kMaxDevices = 64;
 struct Buffer {
     void *ptr = nullptr;
     size_t cap = 0;
+    uint32_t grow_bit = 0;       // engine scratch: its bit of the growth mask (1 << Ws), set when it grows
     bool reserve(size_t bytes);  // grow-only hipMalloc
     void release();              // hipFree (the owning device must be current)
 };
@@ -21,6 +22,64 @@ struct HostBuffer {
     void *dptr = nullptr;  // the same pinned bytes as kernels address them (zero-copy)
     size_t cap = 0;
     bool reserve(size_t bytes);
+};
+
+// The engine's scratch buffers (DeviceCtx::ws_*) in the one order everything that lists
+// them uses: Plan::bytes, fltee_debug_plan's sizes, the bits of fltee_debug_scratch_grown.
+enum Ws { kWsA, kWsB, kWsMat, kWsR, kWsCoef, kWsRec, kWsKeys, kWsRadix, kWsOram, kWsSide,
+          kWsLb, kWsS16, kWsCnt, kWsSel, kWsCount };
+
+// What aggregate() runs for a public shape (Plan::route), and for the `advanced` family how
+// the array is folded and brought to out after its first sort (AdvShape::tail).
+enum Route : uint32_t {
+    kRouteNone,          // refused before a route was chosen (unknown alg)
+    kRouteDense,         // flat algs, FLTEE_OPT_DENSE: the dense accumulate
+    kRouteScatterRows,   // non_oblivious: scatter into per-client rows
+    kRouteCountingFold,  // non_oblivious: ordered fold in the counting sort's order
+    kRouteFlatOrdered,   // baseline / path_oram, k == d: ordered fold by the composite-key network
+    kRouteSweep,         // baseline / path_oram: the ordered sweep
+    kRouteTree,          // path_oram as the tree Path ORAM
+    kRouteTreeLazy,      // ... one access per record, readout through advanced's network
+    kRouteAdvanced,
+    kRouteBubble,        // alg 7: the stable network, then advanced's tail
+    kRouteOptimized,     // alg 6: advanced per batch
+    kRouteNips19,
+};
+enum Tail : uint32_t {
+    kTailNone,
+    kTailFused,     // the fold inside the compaction's first pass (k_compact.hip fc_shape)
+    kTailStream,    // the streaming fold over the compaction's prefix, then the compaction
+    kTailOneEntry,  // d = 1 and no records: the one entry copied, then the compaction
+    kTailSort,      // k_req != k (or the compaction switched off): fold, then the full second sort
+};
+
+// One `advanced` network: n clients' k records over d parameters, folded over fold_len.
+struct AdvShape {
+    size_t nrec = 0, d = 0, L = 0, M = 0, fold_len = 0;
+    size_t halo = 0;    // the effective one: opts.fold_halo, or n
+    size_t span = 0;    // positions the separate fold covers (kTailStream: the compaction's prefix)
+    Tail tail = kTailNone;
+    bool stable = false;  // alg 7: the first sort is the stable network's (k_stable.hip)
+    size_t side_bytes = 0, lb_bytes = 0;
+};
+
+// The one decision about a call's public shape (alg, n, k, d, opts): whether it is refused,
+// what runs, and the bytes of every scratch buffer that touches.  Host arithmetic only.
+// Outside the plan, because they depend on data: nips19's selected list (ws_sel) and the
+// ws_keys / ws_radix its ordered fold sizes from the count read back from the device
+// (ordered_from_list).
+struct Plan {
+    fltee_status_t status = FLTEE_SUCCESS;  // else the refusal; the sizes are still filled in
+    Route route = kRouteNone;
+    bool clip_records = false;  // FLTEE_OPT_CLIP works on a clipped copy of the records
+    AdvShape adv;               // advanced, alg 7, an alg-6 batch, the lazy tree's readout (1 x slots)
+    AdvShape adv_last;          // alg 6: the short last batch (when n % batch)
+    size_t batch = 0;           // alg 6
+    size_t tree_slots = 0;      // the tree ORAM's slots (k_oram.hip oram_slots)
+    size_t kq = 0, tf = 0, L = 0, M = 0;  // nips19 (nips19.rs:38: T from the REQUEST's k)
+    float T = 0.0f;
+    size_t sel_tiles = 0;       // nips19: tiles of the shuffle's selecting last pass (0: select apart)
+    size_t bytes[kWsCount] = {};
 };
 
 struct DeviceCtx {

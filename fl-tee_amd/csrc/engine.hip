@@ -49,6 +49,13 @@ static bool use_scatter_rows(size_t n, size_t k, size_t d) {
 // index's records in upload order).  A public-size decision.
 static bool flat_ordered(size_t n, size_t k, size_t d) { return k == d && n * k > 0; }
 
+// the engine's scratch buffers in Ws order
+static Buffer DeviceCtx::*const kScratch[kWsCount] = {
+    &DeviceCtx::ws_a,    &DeviceCtx::ws_b,    &DeviceCtx::ws_mat,   &DeviceCtx::ws_r,    &DeviceCtx::ws_coef,
+    &DeviceCtx::ws_rec,  &DeviceCtx::ws_keys, &DeviceCtx::ws_radix, &DeviceCtx::ws_oram, &DeviceCtx::ws_side,
+    &DeviceCtx::ws_lb,   &DeviceCtx::ws_s16,  &DeviceCtx::ws_cnt,   &DeviceCtx::ws_sel};
+static std::atomic<uint32_t> g_scratch_grown{0};  // fltee_debug_scratch_grown
+
 static DeviceCtx g_ctx[kMaxDevices];
 static std::mutex g_ctx_mu;
 static std::atomic<uint64_t> g_debug_seed{0};
@@ -125,6 +132,7 @@ DeviceCtx *device_ctx(int dev) {
         if (hipMalloc(&c.status, 256) != hipSuccess) return nullptr;
         if (fl_memset(c.status, 0, 256) != hipSuccess) return nullptr;
         c.device = dev;
+        for (int w = 0; w < kWsCount; ++w) (c.*kScratch[w]).grow_bit = 1u << w;
         c.ready = true;
     }
     return &c;
@@ -138,6 +146,7 @@ DeviceCtx *current_ctx() {
 
 bool Buffer::reserve(size_t bytes) {
     if (bytes <= cap) return true;
+    g_scratch_grown.fetch_or(grow_bit, std::memory_order_relaxed);
     if (ptr) (void)hipFree(ptr);
     ptr = nullptr;
     cap = 0;
@@ -177,113 +186,167 @@ static size_t f32_to_usize_sat(float x) {
     return (size_t)x;
 }
 
-// scratch plan per algorithm
-struct Plan {
-    size_t a_bytes = 0, b_bytes = 0, mat_bytes = 0, r_bytes = 0, coef_bytes = 0, rec_bytes = 0;
-    size_t keys_bytes = 0, radix_bytes = 0;  // ordered fold: sorted records, sort scratch
-    size_t side_bytes = 0;                   // advanced's streaming fold: side records
-    size_t lb_bytes = 0;                     // advanced's fused fold: look-back slots
-    size_t oram_bytes = 0;                   // path_oram tree: slots (16 B) + their records (8 B)
-    size_t s16_bytes = 0;                    // alg 7: the stable network's 16-byte records
-};
+// runtime A/B toggles the plan reads (the fused fold's own, fltee_debug_set_fold_compact,
+// is read through fc_lookback_bytes)
+static bool g_radix_order = true;          // fltee_debug_set_radix_order
+static bool g_advanced_compaction = true;  // fltee_debug_set_advanced_compaction
+static bool g_nips19_fused_select = true;  // fltee_debug_set_nips19_fused_select
+void set_radix_order(int on) { g_radix_order = on != 0; }
 
-// the side records of advanced's streaming fold over its array (M) or its compaction
-// prefix (run_advanced's mf), whichever has more lanes
-static size_t advanced_side_bytes(size_t n, size_t k, size_t d, size_t halo) {
-    const size_t L = n * k + d, M = next_pow2_sz(L);
-    size_t mf = (L + 1 + 15) / 16 * 16;
-    if (mf > M) mf = M;
-    const size_t a = fold_side_bytes(M, M, halo, 0, 0), b = mf >= 2 ? fold_side_bytes(mf, L, halo, 0, 0) : 0;
-    return a > b ? a : b;
+// the positions advanced's separate fold covers in front of the compaction, which
+// reads [0, L) only: up to the first pad (position L is read as the run-end test of
+// L - 1), not the pads after it
+static size_t advanced_fold_span(size_t L, size_t M) {
+    const size_t mf = (L + 1 + 15) / 16 * 16;
+    return mf > M ? M : mf;
+}
+
+// the ordered fold's sort scratch for n records: the counting sort's, or the composite-key
+// network's keys (network_order, or fltee_debug_set_radix_order(0))
+static size_t ordered_radix_bytes(size_t n, size_t d, bool network_order) {
+    return g_radix_order && !network_order ? radix_scratch_bytes(n, d) : next_pow2_sz(n) * 8;
+}
+
+static AdvShape adv_shape(size_t n, size_t k, size_t d, size_t k_req, size_t halo) {
+    AdvShape a;
+    a.nrec = n * k, a.d = d, a.L = n * k + d, a.M = next_pow2_sz(a.L);
+    a.fold_len = n * k_req + d, a.halo = halo ? halo : n, a.span = a.M;
+    // Second sort (advanced.rs:106-111): with fold_len == L its [0, d) prefix is the
+    // order-preserving compaction of the idx < d representatives (k_compact.hip), and
+    // the fold runs inside the compaction's first pass where fc_shape takes it; the
+    // k_req != k quirk leaves unfolded records competing for that prefix and keeps the
+    // full network.
+    if (a.fold_len != a.L || !g_advanced_compaction) {
+        a.tail = kTailSort;
+    } else if ((a.lb_bytes = fc_lookback_bytes(a.M, a.L, d, a.halo)) != 0) {
+        a.tail = kTailFused;
+    } else {
+        a.span = advanced_fold_span(a.L, a.M);
+        a.tail = a.span >= 2 ? kTailStream : kTailOneEntry;
+    }
+    if (a.tail != kTailFused) a.side_bytes = fold_side_bytes(a.span, a.fold_len, a.halo, 0, 0);
+    return a;
+}
+
+static void plan_adv_bytes(Plan &p, const AdvShape &a) {
+    auto up = [&p](Ws w, size_t b) { if (b > p.bytes[w]) p.bytes[w] = b; };
+    up(kWsA, a.M * 8), up(kWsB, a.M * 8), up(kWsSide, a.side_bytes), up(kWsLb, a.lb_bytes);
+    if (a.stable) up(kWsS16, a.M * 16);
 }
 
 static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
     Plan p;
     const bool dense = (o.flags & FLTEE_OPT_DENSE) != 0;
-    const bool clip = (o.flags & FLTEE_OPT_CLIP) != 0;
-    // (aggregate() refuses a tree shape that does not fit before it plans: tree_shape)
     const bool tree = alg == FLTEE_ALG_PATH_ORAM && (o.flags & FLTEE_OPT_ORAM_TREE);
-    if (clip) {
-        p.coef_bytes = n * 4;
-        if (!dense || tree) p.rec_bytes = n * k * 8;  // the tree reads records: clipped copies
+    const size_t nrec = n * k, k_req = (o.flags & FLTEE_OPT_K_REQ) ? o.k_req : k;
+    auto refuse_if = [&p](bool bad) { if (bad) p.status = FLTEE_ERROR_INVALID_PARAMETER; };
+    // 32-bit positions; a dense upload has one record per parameter
+    refuse_if(n == 0 || nrec + d >= ((size_t)1 << 31) || (dense && k != d));
+    if (o.flags & FLTEE_OPT_CLIP) {
+        p.bytes[kWsCoef] = n * 4;
+        p.clip_records = !dense || tree;  // the tree reads records
+        if (p.clip_records) p.bytes[kWsRec] = nrec * 8;
     }
     switch (alg) {
     case FLTEE_ALG_PATH_ORAM:
-        if (tree) {
-            const bool lazy = (o.flags & FLTEE_OPT_ORAM_LAZY) != 0;
-            const size_t ns = oram_slots(d);
-            p.oram_bytes = ns * (lazy ? 24 : 16);
-            // the leaf precompute's two key arrays; lazy: the readout network too
-            size_t m = next_pow2_sz(oram_accesses(n * k, d, lazy));
-            if (lazy && next_pow2_sz(ns + d) > m) m = next_pow2_sz(ns + d);
-            p.a_bytes = p.b_bytes = m * 8;
-        } else if (!dense && flat_ordered(n, k, d)) {
-            p.keys_bytes = n * k * 8, p.radix_bytes = next_pow2_sz(n * k) * 8;
-        }
-        break;
     case FLTEE_ALG_BASELINE:
-        if (!dense && flat_ordered(n, k, d))  // the composite-key network + its gather
-            p.keys_bytes = n * k * 8, p.radix_bytes = next_pow2_sz(n * k) * 8;
-        break;
     case FLTEE_ALG_NON_OBLIVIOUS:
-        if (!dense) {
-            if (use_scatter_rows(n, k, d)) p.mat_bytes = n * d * 4;
-            else p.keys_bytes = n * k * 8, p.radix_bytes = radix_scratch_bytes(n * k, d);
+        if (tree) {
+            // a shape outside oram_fits is refused (the ECALL gates the tree on the same
+            // predicate and takes the sweep instead)
+            const bool lazy = (o.flags & FLTEE_OPT_ORAM_LAZY) != 0;
+            p.route = lazy ? kRouteTreeLazy : kRouteTree;
+            refuse_if(!oram_fits(nrec, d, lazy));
+            p.tree_slots = oram_slots(d);
+            p.bytes[kWsOram] = p.tree_slots * (lazy ? 24 : 16);  // slots, lazy: their records too
+            // the leaf precompute's two key arrays
+            p.bytes[kWsA] = p.bytes[kWsB] = next_pow2_sz(oram_accesses(nrec, d, lazy)) * 8;
+            // lazy readout: every slot's (idx, value) through advanced's network (one
+            // "client" of `slots` records: each index at most once, runs of <= 2 entries)
+            if (lazy) plan_adv_bytes(p, p.adv = adv_shape(1, p.tree_slots, d, p.tree_slots, 1));
+        } else if (dense) {
+            p.route = kRouteDense;
+        } else if (alg == FLTEE_ALG_NON_OBLIVIOUS && use_scatter_rows(n, k, d)) {
+            p.route = kRouteScatterRows;
+            p.bytes[kWsMat] = n * d * 4;
+        } else if (alg == FLTEE_ALG_NON_OBLIVIOUS || flat_ordered(n, k, d)) {
+            const bool net = alg != FLTEE_ALG_NON_OBLIVIOUS;
+            p.route = net ? kRouteFlatOrdered : kRouteCountingFold;
+            refuse_if(next_pow2_sz(nrec) > kMaxNetRecords);
+            p.bytes[kWsKeys] = nrec * 8, p.bytes[kWsRadix] = ordered_radix_bytes(nrec, d, net);
+        } else {
+            p.route = kRouteSweep;
         }
         break;
-    case FLTEE_ALG_BUBBLE:  // advanced's arrays behind the stable network's own
-        p.s16_bytes = next_pow2_sz(n * k + d) * 16;
-        [[fallthrough]];
+    case FLTEE_ALG_BUBBLE:
+        // bubble_sort_based.rs:42 folds n * k_req + d entries; only k_req == k is answered
+        p.route = kRouteBubble;
+        p.adv = adv_shape(n, k, d, k, o.fold_halo);
+        p.adv.stable = true;
+        refuse_if(k_req != k || p.adv.M > kMaxNetRecords || p.adv.M > stable_sort_max_records());
+        plan_adv_bytes(p, p.adv);
+        break;
     case FLTEE_ALG_ADVANCED:
-        p.a_bytes = p.b_bytes = next_pow2_sz(n * k + d) * 8;
-        p.side_bytes = advanced_side_bytes(n, k, d, o.fold_halo ? o.fold_halo : n);
-        p.lb_bytes = fc_lookback_bytes(next_pow2_sz(n * k + d), n * k + d, d, o.fold_halo ? o.fold_halo : n);
+        p.route = kRouteAdvanced;
+        p.adv = adv_shape(n, k, d, k_req, o.fold_halo);
+        refuse_if(p.adv.M > kMaxNetRecords || p.adv.fold_len > p.adv.L);  // advanced.rs:72 panic
+        plan_adv_bytes(p, p.adv);
         break;
-    case FLTEE_ALG_OPTIMIZED: {
-        size_t b = o.batch ? (o.batch < n ? o.batch : n) : n;
-        p.a_bytes = p.b_bytes = next_pow2_sz(b * k + d) * 8;
-        p.side_bytes = advanced_side_bytes(b, k, d, o.fold_halo ? o.fold_halo : b);
-        p.lb_bytes = fc_lookback_bytes(next_pow2_sz(b * k + d), b * k + d, d, o.fold_halo ? o.fold_halo : b);
+    case FLTEE_ALG_OPTIMIZED:
+        p.route = kRouteOptimized;
+        p.batch = o.batch && o.batch < n ? o.batch : n;
+        p.adv = adv_shape(p.batch, k, d, k, o.fold_halo);
+        refuse_if(p.adv.M > kMaxNetRecords);
+        plan_adv_bytes(p, p.adv);
+        if (p.batch && n % p.batch)
+            plan_adv_bytes(p, p.adv_last = adv_shape(n % p.batch, k, d, k, o.fold_halo));
         break;
-    }
-    case FLTEE_ALG_NIPS19: {
-        const size_t kq = (o.flags & FLTEE_OPT_K_REQ) ? o.k_req : k;  // nips19.rs:38
-        const float T = nips19_threshold(d, kq, n);
-        p.a_bytes = next_pow2_sz(n * k + d * f32_to_usize_sat(T)) * 8;
-        p.r_bytes = d * 4;
+    case FLTEE_ALG_NIPS19:
+        p.route = kRouteNips19;
+        p.kq = k_req;
+        p.T = nips19_threshold(d, p.kq, n);
+        p.tf = f32_to_usize_sat(p.T);
+        p.bytes[kWsR] = d * 4;
+        refuse_if(p.tf > ((size_t)1 << 31) / (d ? d : 1));
+        if (p.status != FLTEE_SUCCESS) break;  // (d * tf would overflow)
+        p.L = nrec + d * p.tf, p.M = next_pow2_sz(p.L);
+        refuse_if(p.M > kMaxNetRecords);
+        p.bytes[kWsA] = p.M * 8;
+        // the tile counts: the shuffle's selecting last pass, or (where that launcher
+        // declines) safe_aggregate's own tiles
+        p.sel_tiles = g_nips19_fused_select && d ? bitonic_select_tiles(p.M) : 0;
+        p.bytes[kWsCnt] = (2 * (p.sel_tiles > select_tiles(p.M) ? p.sel_tiles : select_tiles(p.M)) + 2) * 4;
         break;
-    }
-    default: break;
+    default:
+        refuse_if(true);  // lib.rs:396 panics on unknown algs
+        break;
     }
     return p;
 }
 
-// the fused fold's look-back slots: grown zeroed (a stale slot must never carry a live
-// epoch), the epochs starting over
-static bool reserve_lb(DeviceCtx *c, size_t bytes) {
-    if (bytes <= c->ws_lb.cap) return true;
-    if (!c->ws_lb.reserve(bytes) || fl_memset(c->ws_lb.ptr, 0, c->ws_lb.cap) != hipSuccess) return false;
+// The fused fold's look-back slots, ready for one more launch.  A slot must never carry a
+// live epoch it was not given: new slots hold whatever was there, and at epoch 2^30 - 1 the
+// counter would wrap into epochs old slots still hold — either way the slots are zeroed and
+// the epochs start over.  s: the stream the launch follows on (in front of every fused
+// launch: the slots of launches before it on that stream may still be read); none
+// (fltee_reserve): grow only, zeroed on the host's time.
+static bool reserve_lb(DeviceCtx *c, size_t bytes, const hipStream_t *s) {
+    const bool grow = bytes > c->ws_lb.cap;
+    if (!bytes || (!grow && (!s || c->fc_epoch < (1u << 30) - 1))) return true;
+    if (!c->ws_lb.reserve(bytes)) return false;
+    if ((s ? fl_memset_async(c->ws_lb.ptr, 0, c->ws_lb.cap, *s) : fl_memset(c->ws_lb.ptr, 0, c->ws_lb.cap)) !=
+        hipSuccess)
+        return false;
     c->fc_epoch = 0;
     return true;
 }
 
-static bool reserve_plan(DeviceCtx *c, const Plan &p) {
-    return c->ws_a.reserve(p.a_bytes) && c->ws_b.reserve(p.b_bytes) &&
-           c->ws_mat.reserve(p.mat_bytes) && c->ws_r.reserve(p.r_bytes) &&
-           c->ws_coef.reserve(p.coef_bytes) && c->ws_rec.reserve(p.rec_bytes) &&
-           c->ws_keys.reserve(p.keys_bytes) && c->ws_radix.reserve(p.radix_bytes) &&
-           c->ws_oram.reserve(p.oram_bytes) && c->ws_side.reserve(p.side_bytes) &&
-           c->ws_s16.reserve(p.s16_bytes) && reserve_lb(c, p.lb_bytes);
+static bool reserve_plan(DeviceCtx *c, const Plan &p, const hipStream_t *s) {
+    for (int w = 0; w < kWsCount; ++w)
+        if (!(w == kWsLb ? reserve_lb(c, p.bytes[w], s) : (c->*kScratch[w]).reserve(p.bytes[w]))) return false;
+    return true;
 }
 
-// The ordered fold of n records (common.rs:25-35, non_oblivious.rs:11-13): the records in
-// stable order by idx, then out[i] = the in-order sum of index i's.  The order comes from
-// the hand-written counting sort (k_radix.hip: the sequence of indices in list order is
-// what the enclave's own g[idx] += val loop touches) — or, fltee_debug_set_radix_order(0),
-// from the composite-key bitonic sort, the records gathered by its keys (the same order,
-// bit for bit: test_gpu_parity.py).
-static bool g_radix_order = true;
-void set_radix_order(int on) { g_radix_order = on != 0; }
 static bool g_exact_runs = false;  // the ECALLs' advanced / alg 6: reject runs > n + 1 unless set
 void set_exact_runs(int on) { g_exact_runs = on != 0; }
 bool exact_runs_default() { return g_exact_runs; }
@@ -294,20 +357,25 @@ static bool g_oram_tree = false;  // the ECALLs' path_oram: the sweep unless set
 void set_oram_tree(int on) { g_oram_tree = on != 0; }
 bool oram_tree_default() { return g_oram_tree; }
 
+// The ordered fold of n records (common.rs:25-35, non_oblivious.rs:11-13): the records in
+// stable order by idx, then out[i] = the in-order sum of index i's.  The order comes from
+// the hand-written counting sort (k_radix.hip: the sequence of indices in list order is
+// what the enclave's own g[idx] += val loop touches) — or, fltee_debug_set_radix_order(0),
+// from the composite-key bitonic sort, the records gathered by its keys (the same order,
+// bit for bit: test_gpu_parity.py).
+// ws_keys (n * 8) and ws_radix (ordered_radix_bytes) are the caller's: the plan's, or
+// ordered_from_list's.
 static hipError_t ordered_fold_records(DeviceCtx *c, const void *rec, size_t n, size_t d,
                                        float coef, float *out, bool acc, uint32_t *status,
                                        hipStream_t s, bool network_order = false) {
     if (n == 0) return acc ? hipSuccess : fl_memset_async(out, 0, d * 4, s);
-    if (!c->ws_keys.reserve(n * 8)) return hipErrorOutOfMemory;
     uint64_t *sorted = (uint64_t *)c->ws_keys.ptr;
     hipError_t e;
     if (g_radix_order && !network_order) {
-        if (!c->ws_radix.reserve(radix_scratch_bytes(n, d))) return hipErrorOutOfMemory;
         e = launch_sort_records_by_idx(rec, n, d, c->ws_radix.ptr, c->ws_radix.cap, sorted, status,
                                        acc ? nullptr : out, d, s);
     } else {
         const size_t mc = next_pow2_sz(n);
-        if (!c->ws_radix.reserve(mc * 8)) return hipErrorOutOfMemory;
         uint64_t *keys = (uint64_t *)c->ws_radix.ptr;
         e = launch_composite_init(rec, n, d, mc, keys, status, s);
         if (e == hipSuccess) e = bitonic_sort(keys, mc, 1, 0, s, n);  // ~0 keys past n
@@ -319,10 +387,12 @@ static hipError_t ordered_fold_records(DeviceCtx *c, const void *rec, size_t n, 
 }
 
 // the selected list sel[0, lc) (entries with idx < d in position order) -> out: stable
-// order by idx (list position within an index), then the ordered fold
+// order by idx (list position within an index), then the ordered fold.  lc was read back
+// from the device: the one scratch sized here, outside the plan.
 hipError_t ordered_from_list(DeviceCtx *c, const uint64_t *sel, size_t lc, size_t d, float coef,
                              float *out, bool acc, uint32_t *status, hipStream_t s) {
-    if (lc == 0) return acc ? hipSuccess : fl_memset_async(out, 0, d * 4, s);
+    if (lc && (!c->ws_keys.reserve(lc * 8) || !c->ws_radix.reserve(ordered_radix_bytes(lc, d, false))))
+        return hipErrorOutOfMemory;
     return ordered_fold_records(c, sel, lc, d, coef, out, acc, status, s);
 }
 
@@ -357,19 +427,19 @@ hipError_t safe_aggregate_ordered(DeviceCtx *c, const uint64_t *src, size_t m, s
 }
 
 // nips19's shuffle + safe_aggregate with the selection fused into the shuffle's last
-// pass (bitonic_sort_nips19_select): the 2^27-entry array is never written out or read
-// back.  hipErrorNotSupported: shape not fusable (the caller shuffles, then selects).
-static hipError_t nips19_shuffle_aggregate(DeviceCtx *c, uint64_t *A, size_t M, uint32_t key,
-                                           const void *rec, size_t nrec, const uint32_t *r,
-                                           size_t d, size_t tf, float coef, float *out, bool acc,
+// pass (bitonic_sort_nips19_select, over the plan's sel_tiles tiles): the 2^27-entry array
+// is never written out or read back.  hipErrorNotSupported: the launcher declined (the
+// caller shuffles, then selects).
+static hipError_t nips19_shuffle_aggregate(DeviceCtx *c, const Plan &p, uint32_t key, const void *rec,
+                                           size_t nrec, size_t d, float coef, float *out, bool acc,
                                            uint32_t *status, hipStream_t s) {
-    const size_t ntl = bitonic_select_tiles(M);
-    if (ntl == 0 || d == 0) return hipErrorNotSupported;
-    if (!c->ws_cnt.reserve((2 * ntl + 2) * 4)) return hipErrorOutOfMemory;
+    const size_t ntl = p.sel_tiles;
+    uint64_t *A = (uint64_t *)c->ws_a.ptr;
     uint32_t *cnt = (uint32_t *)c->ws_cnt.ptr, *base = cnt + ntl + 1;
     // tiles of pads alone are skipped by the last pass and keep a zero count
     hipError_t e = fl_memset_async(cnt, 0, ntl * 4, s);
-    if (e == hipSuccess) e = bitonic_sort_nips19_select(A, M, key, rec, nrec, r, d, tf, cnt, s);
+    if (e == hipSuccess)
+        e = bitonic_sort_nips19_select(A, p.M, key, rec, nrec, (const uint32_t *)c->ws_r.ptr, d, p.tf, cnt, s);
     if (e != hipSuccess) return e;
     e = launch_select_scan(cnt, ntl, base, s);
     size_t lc = 0;
@@ -377,82 +447,48 @@ static hipError_t nips19_shuffle_aggregate(DeviceCtx *c, uint64_t *A, size_t M, 
     if (e != hipSuccess) return e;
     if (!c->ws_sel.reserve(lc * 8 + 8)) return hipErrorOutOfMemory;
     uint64_t *sel = (uint64_t *)c->ws_sel.ptr;
-    if (lc) e = launch_select_gather(A, log2_pow2(M / ntl), ntl, cnt, base, sel, s);
+    if (lc) e = launch_select_gather(A, log2_pow2(p.M / ntl), ntl, cnt, base, sel, s);
     if (e != hipSuccess) return e;
     return ordered_from_list(c, sel, lc, d, coef, out, acc, status, s);
 }
 
-// `advanced` over n clients' records into out (coef or accumulate).
-static bool g_advanced_compaction = true;  // fltee_debug_set_advanced_compaction
-static bool g_nips19_fused_select = true;  // fltee_debug_set_nips19_fused_select (A/B)
-
-// the positions run_advanced's separate fold covers in front of the compaction, which
-// reads [0, L) only: up to the first pad (position L is read as the run-end test of
-// L - 1), not the pads after it
-static size_t advanced_fold_span(size_t L, size_t M) {
-    const size_t mf = (L + 1 + 15) / 16 * 16;
-    return mf > M ? M : mf;
-}
-
-// stable: alg 7 — the array is sorted by (idx, upload position) through the stable
-// network (k_stable.hip) instead of advanced's first sort; everything after it is shared.
-static hipError_t run_advanced(DeviceCtx *c, const void *rec, size_t n, size_t k, size_t d,
-                               size_t k_req, size_t halo, float coef, float *out, bool acc,
-                               uint32_t *status, hipStream_t s, bool stable = false) {
-    const size_t L = n * k + d, M = next_pow2_sz(L);
-    const size_t fold_len = n * k_req + d;
+// `advanced` over the planned shape's records into out (coef or accumulate), on scratch the
+// plan reserved.  a.stable (alg 7): the array is sorted by (idx, upload position) through
+// the stable network (k_stable.hip) instead of advanced's first sort; the tail is shared.
+static hipError_t run_advanced(DeviceCtx *c, const void *rec, const AdvShape &a, float coef, float *out,
+                               bool acc, uint32_t *status, hipStream_t s) {
     uint64_t *A = (uint64_t *)c->ws_a.ptr, *B = (uint64_t *)c->ws_b.ptr;
     hipError_t e;
-    if (stable) {  // init fused into the first pass, strip into the last
-        e = stable_sort(c->ws_s16.ptr, M, s, L, true, rec, n * k, d, A);
+    if (a.stable) {  // init fused into the first pass, strip into the last
+        e = stable_sort(c->ws_s16.ptr, a.M, s, a.L, true, rec, a.nrec, a.d, A);
     } else {
-        e = bitonic_sort_advanced(A, M, rec, n * k, d, s);  // init fused into the sort
+        e = bitonic_sort_advanced(A, a.M, rec, a.nrec, a.d, s);  // init fused into the sort
         if (e == hipErrorNotSupported) {
-            e = launch_advanced_init(rec, n * k, d, M, A, s);
-            if (e == hipSuccess) e = bitonic_sort(A, M, 0, 0, s, L);
+            e = launch_advanced_init(rec, a.nrec, a.d, a.M, A, s);
+            if (e == hipSuccess) e = bitonic_sort(A, a.M, 0, 0, s, a.L);
         }
     }
     if (e != hipSuccess) return e;
-    // Second sort (advanced.rs:106-111): with fold_len == L its [0, d) prefix is the
-    // order-preserving compaction of the idx < d representatives (k_compact.hip), and
-    // the fold runs inside the compaction's first pass; the k_req != k quirk leaves
-    // unfolded records competing for that prefix and keeps the full network.
-    if (fold_len == L && g_advanced_compaction) {
-        const size_t lbb = fc_lookback_bytes(M, L, d, halo ? halo : n);
-        if (lbb && (lbb > c->ws_lb.cap || c->fc_epoch >= (1u << 30) - 1)) {
-            // new slots hold whatever was there: zero them (the epochs start over)
-            if (!c->ws_lb.reserve(lbb) || fl_memset_async(c->ws_lb.ptr, 0, c->ws_lb.cap, s) != hipSuccess)
-                return hipErrorOutOfMemory;
-            c->fc_epoch = 0;
-        }
-        e = launch_fold_compact_extract(A, B, M, L, d, halo ? halo : n, coef, out, acc, status, s,
-                                        c->ws_lb.ptr, c->ws_lb.cap, &c->fc_epoch);
-        if (e != hipErrorNotSupported) return e;
-    }
-    if (fold_len == L && g_advanced_compaction) {
-        const size_t mf = advanced_fold_span(L, M);
-        // the fold emits the compaction's first-pass form (no conversion there, 16-B pairs);
-        // a one-entry array — d = 1 and no records — has nothing to fold: copied as the
-        // enclave's folded array and converted by that pass
-        if (!c->ws_side.reserve(fold_side_bytes(mf, fold_len, halo ? halo : n, 0, 0)))
-            return hipErrorOutOfMemory;
-        if (mf >= 2) {
-            e = launch_fold(A, B, mf, fold_len, halo ? halo : n, c->ws_side.ptr, c->ws_side.cap, s,
-                            d, compact_dummy());
-            if (e != hipSuccess) return e;
-            return launch_compact_extract_converted(B, A, L, d, coef, out, acc, s);
-        }
-        e = launch_fold(A, B, mf, fold_len, halo ? halo : n, c->ws_side.ptr, c->ws_side.cap, s);
+    switch (a.tail) {
+    case kTailFused:
+        if (!reserve_lb(c, a.lb_bytes, &s)) return hipErrorOutOfMemory;  // (the epoch wrap: no growth here)
+        return launch_fold_compact_extract(A, B, a.M, a.L, a.d, a.halo, coef, out, acc, status, s,
+                                           c->ws_lb.ptr, c->ws_lb.cap, &c->fc_epoch);
+    case kTailStream:  // the fold emits the compaction's first-pass form (no conversion there, 16-B pairs)
+        e = launch_fold(A, B, a.span, a.fold_len, a.halo, c->ws_side.ptr, c->ws_side.cap, s, a.d,
+                        compact_dummy());
         if (e != hipSuccess) return e;
-        return launch_compact_extract(B, A, L, d, coef, out, acc, s);
+        return launch_compact_extract_converted(B, A, a.L, a.d, coef, out, acc, s);
+    case kTailOneEntry:  // nothing to fold: copied as the enclave's folded array, converted by that pass
+        e = launch_fold(A, B, a.span, a.fold_len, a.halo, c->ws_side.ptr, c->ws_side.cap, s);
+        if (e != hipSuccess) return e;
+        return launch_compact_extract(B, A, a.L, a.d, coef, out, acc, s);
+    default:
+        e = launch_fold(A, B, a.M, a.fold_len, a.halo, c->ws_side.ptr, c->ws_side.cap, s);
+        if (e == hipSuccess) e = bitonic_sort(B, a.M, 0, 0, s, a.L);  // the fold copies the pads past fold_len
+        if (e == hipSuccess) e = launch_extract(B, a.d, coef, out, acc, s);
+        return e;
     }
-    if (!c->ws_side.reserve(fold_side_bytes(M, fold_len, halo ? halo : n, 0, 0)))
-        return hipErrorOutOfMemory;
-    e = launch_fold(A, B, M, fold_len, halo ? halo : n, c->ws_side.ptr, c->ws_side.cap, s);
-    if (e != hipSuccess) return e;
-    e = bitonic_sort(B, M, 0, 0, s, L);  // the fold copies the pads past fold_len
-    if (e == hipSuccess) e = launch_extract(B, d, coef, out, acc, s);
-    return e;
 }
 
 // `advanced` of n clients' records into out[d] un-averaged (coef 1, overwrite): one
@@ -463,52 +499,24 @@ hipError_t advanced_batch(const void *rec, size_t n, size_t k, size_t d, size_t 
     if (!c) return hipErrorInvalidDevice;
     fltee_device_opts o;
     std::memset(&o, 0, sizeof o);
-    if (!reserve_plan(c, plan_for(FLTEE_ALG_ADVANCED, n, k, d, o))) return hipErrorOutOfMemory;
-    return run_advanced(c, rec, n, k, d, k, halo, 1.0f, out, false, status, s);
+    o.fold_halo = halo;
+    const Plan p = plan_for(FLTEE_ALG_ADVANCED, n, k, d, o);
+    if (p.status != FLTEE_SUCCESS) return hipErrorInvalidValue;
+    if (!reserve_plan(c, p, &s)) return hipErrorOutOfMemory;
+    return run_advanced(c, rec, p.adv, 1.0f, out, false, status, s);
 }
 
+// plan -> the refusal -> the plan's scratch -> clip -> the route -> DP
 fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size_t d, float *out,
                          const fltee_device_opts &o, hipStream_t s, uint32_t *status) {
     DeviceCtx *c = current_ctx();
     if (!c) return FLTEE_ERROR_UNEXPECTED;
-    if (n == 0) return FLTEE_ERROR_INVALID_PARAMETER;
-    if (n * k + d >= ((size_t)1 << 31)) return FLTEE_ERROR_INVALID_PARAMETER;  // 32-bit positions
-    // the networks address records with 32-bit byte offsets: arrays of <= 2^29 records
-    // (k_bitonic.hip, k_compact.hip); refuse larger ones before reserving scratch
-    constexpr size_t kMaxNet = (size_t)1 << 29;
-    if (alg == FLTEE_ALG_BUBBLE) {
-        // bubble_sort_based.rs:42 folds n * k_req + d entries; only k_req == k is answered
-        if ((o.flags & FLTEE_OPT_K_REQ) && o.k_req != k) return FLTEE_ERROR_INVALID_PARAMETER;
-        if (next_pow2_sz(n * k + d) > kMaxNet || next_pow2_sz(n * k + d) > stable_sort_max_records())
-            return FLTEE_ERROR_INVALID_PARAMETER;
-    }
-    if ((alg == FLTEE_ALG_ADVANCED && next_pow2_sz(n * k + d) > kMaxNet) ||
-        (alg == FLTEE_ALG_OPTIMIZED &&
-         next_pow2_sz((o.batch && o.batch < n ? o.batch : n) * k + d) > kMaxNet) ||
-        (alg == FLTEE_ALG_NON_OBLIVIOUS && !(o.flags & FLTEE_OPT_DENSE) &&
-         !use_scatter_rows(n, k, d) && next_pow2_sz(n * k) > kMaxNet))
-        return FLTEE_ERROR_INVALID_PARAMETER;
-    // the tree Path ORAM: a shape outside oram_fits is refused before any scratch is sized
-    // for it (the ECALL gates the tree on the same predicate and takes the sweep instead)
-    const bool tree = alg == FLTEE_ALG_PATH_ORAM && (o.flags & FLTEE_OPT_ORAM_TREE);
-    if (tree && !oram_fits(n * k, d, (o.flags & FLTEE_OPT_ORAM_LAZY) != 0))
-        return FLTEE_ERROR_INVALID_PARAMETER;
-    if ((alg == FLTEE_ALG_BASELINE || (alg == FLTEE_ALG_PATH_ORAM && !tree)) &&
-        !(o.flags & FLTEE_OPT_DENSE) && flat_ordered(n, k, d) && next_pow2_sz(n * k) > kMaxNet)
-        return FLTEE_ERROR_INVALID_PARAMETER;
-    if (alg == FLTEE_ALG_NIPS19) {
-        const size_t kq = (o.flags & FLTEE_OPT_K_REQ) ? o.k_req : k;
-        const size_t tf = f32_to_usize_sat(nips19_threshold(d, kq, n));
-        if (tf > ((size_t)1 << 31) / (d ? d : 1) || next_pow2_sz(n * k + d * tf) > kMaxNet)
-            return FLTEE_ERROR_INVALID_PARAMETER;
-    }
-    const bool dense = (o.flags & FLTEE_OPT_DENSE) != 0;
-    if (dense && k != d) return FLTEE_ERROR_INVALID_PARAMETER;
+    const Plan p = plan_for(alg, n, k, d, o);
+    if (p.status != FLTEE_SUCCESS) return p.status;
+    if (!reserve_plan(c, p, &s)) return FLTEE_ERROR_OUT_OF_MEMORY;
     const bool acc = (o.flags & FLTEE_OPT_ACCUMULATE) != 0;
     const size_t n_avg = o.n_avg ? o.n_avg : n;
     const float coef = (o.flags & FLTEE_OPT_NO_AVERAGE) ? 1.0f : 1.0f / (float)n_avg;
-    const Plan p = plan_for(alg, n, k, d, o);
-    if (!reserve_plan(c, p)) return FLTEE_ERROR_OUT_OF_MEMORY;
 
     // per-client L2 clip (update.py:187-204), off by default
     const float *ccoef = nullptr;
@@ -517,7 +525,7 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
         if (launch_client_clip_coef(rec, n, k, o.clipping, cf, s) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
         ccoef = cf;
-        if (!dense || tree) {  // plan_for reserved ws_rec on the same predicate
+        if (p.clip_records) {
             if (fl_memcpy_async(c->ws_rec.ptr, rec, n * k * 8, hipMemcpyDeviceToDevice, s) != hipSuccess ||
                 launch_apply_clip(c->ws_rec.ptr, n, k, cf, s) != hipSuccess)
                 return FLTEE_ERROR_UNEXPECTED;
@@ -526,107 +534,87 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     }
 
     hipError_t e = hipSuccess;
-    switch (alg) {
-    case FLTEE_ALG_PATH_ORAM:
-        if (tree) {  // the tree Path ORAM (k_oram.hip); oram_fits checked above
-            const bool lazy = (o.flags & FLTEE_OPT_ORAM_LAZY) != 0;
-            const size_t ns = oram_slots(d);
-            uint8_t *tree = (uint8_t *)c->ws_oram.ptr;
-            uint64_t *recs = lazy ? (uint64_t *)(tree + ns * 16) : nullptr;
-            const uint64_t seed = o.seed ? o.seed : next_seed();
-            e = launch_check_range(rec, n * k, (uint32_t)next_pow2_sz(d), status, s);  // oram.rs panics
-            if (e == hipSuccess)
-                e = launch_oram_tree(rec, n * k, d, lazy, tree, seed, (uint64_t *)c->ws_a.ptr,
-                                     (uint64_t *)c->ws_b.ptr, recs, coef, acc, out, status, s);
-            // lazy readout: every slot's (idx, value) through advanced's oblivious network
-            // (one "client" of ns records: each index at most once, runs of <= 2 entries)
-            if (e == hipSuccess && lazy) e = run_advanced(c, recs, 1, ns, d, ns, 1, coef, out, acc, status, s);
-            break;
-        }
-        [[fallthrough]];
-    case FLTEE_ALG_BASELINE:
-    case FLTEE_ALG_NON_OBLIVIOUS:
-        if (dense) {
-            e = launch_dense_accumulate(rec, n, d, coef, out, ccoef, acc, status, s);
-        } else if (alg == FLTEE_ALG_NON_OBLIVIOUS && use_scatter_rows(n, k, d)) {
-            if (c->mat_clean_ptr != c->ws_mat.ptr || c->mat_clean_cap != c->ws_mat.cap) {
-                c->mat_clean = 0;  // a new allocation: contents unknown
-                c->mat_clean_ptr = c->ws_mat.ptr;
-                c->mat_clean_cap = c->ws_mat.cap;
-            }
-            e = launch_scatter_sum(rec, n, k, d, (uint32_t *)c->ws_mat.ptr, &c->mat_clean,
-                                   c->status + 16, coef, out, acc, status, s);
-            if (e != hipSuccess) c->mat_clean = 0;  // the emptying pass may not have run
-        } else if (alg == FLTEE_ALG_NON_OBLIVIOUS) {
-            e = ordered_fold_records(c, rec, n * k, d, coef, out, acc, status, s);
-        } else {
-            // baseline / path_oram on sparse uploads: the ordered sweep (exact for any
-            // upload, a client may repeat an index; fixed cost n*k*d compare-selects) —
-            // or, for dense-sized uploads (flat_ordered), the composite-key network's
-            // ordered fold (exact for any upload too).  Records with idx >= d are ignored
-            // (o_update's compare never matches): the network's range flag goes to a
-            // scratch word.
-            if (alg == FLTEE_ALG_PATH_ORAM)  // oram.rs: blocks beyond next_pow2(d) do not exist
-                e = launch_check_range(rec, n * k, (uint32_t)next_pow2_sz(d), status, s);
-            if (e == hipSuccess && flat_ordered(n, k, d))
-                e = ordered_fold_records(c, rec, n * k, d, coef, out, acc, c->status + 32, s, true);
-            else if (e == hipSuccess)
-                e = launch_sweep_accumulate(rec, n * k, d, coef, out, acc, s);
-        }
-        break;
-    case FLTEE_ALG_ADVANCED: {
-        const size_t k_req = (o.flags & FLTEE_OPT_K_REQ) ? o.k_req : k;
-        const size_t fold_len = n * k_req + d;
-        if (fold_len > n * k + d) return FLTEE_ERROR_INVALID_PARAMETER;  // advanced.rs:72 panic
-        e = run_advanced(c, rec, n, k, d, k_req, o.fold_halo, coef, out, acc, status, s);
+    switch (p.route) {
+    case kRouteTree:
+    case kRouteTreeLazy: {  // the tree Path ORAM (k_oram.hip)
+        const bool lazy = p.route == kRouteTreeLazy;
+        uint8_t *tree = (uint8_t *)c->ws_oram.ptr;
+        uint64_t *recs = lazy ? (uint64_t *)(tree + p.tree_slots * 16) : nullptr;
+        const uint64_t seed = o.seed ? o.seed : next_seed();
+        e = launch_check_range(rec, n * k, (uint32_t)next_pow2_sz(d), status, s);  // oram.rs panics
+        if (e == hipSuccess)
+            e = launch_oram_tree(rec, n * k, d, lazy, tree, seed, (uint64_t *)c->ws_a.ptr,
+                                 (uint64_t *)c->ws_b.ptr, recs, coef, acc, out, status, s);
+        // lazy readout: every slot's (idx, value) through advanced's oblivious network
+        if (e == hipSuccess && lazy) e = run_advanced(c, recs, p.adv, coef, out, acc, status, s);
         break;
     }
-    case FLTEE_ALG_BUBBLE:  // the stable sort, then advanced's fold / compaction / extract
-        e = run_advanced(c, rec, n, k, d, k, o.fold_halo, coef, out, acc, status, s, true);
+    case kRouteDense:
+        e = launch_dense_accumulate(rec, n, d, coef, out, ccoef, acc, status, s);
         break;
-    case FLTEE_ALG_OPTIMIZED: {
-        const size_t batch = o.batch ? o.batch : n;
-        if (!acc) e = fl_memset_async(out, 0, d * 4, s);
-        for (size_t c0 = 0; e == hipSuccess && c0 < n; c0 += batch) {
-            const size_t nb = (c0 + batch < n) ? batch : n - c0;
-            e = run_advanced(c, (const uint8_t *)rec + c0 * k * 8, nb, k, d, k, o.fold_halo, 1.0f,
-                             out, true, status, s);
+    case kRouteScatterRows:
+        if (c->mat_clean_ptr != c->ws_mat.ptr || c->mat_clean_cap != c->ws_mat.cap) {
+            c->mat_clean = 0;  // a new allocation: contents unknown
+            c->mat_clean_ptr = c->ws_mat.ptr;
+            c->mat_clean_cap = c->ws_mat.cap;
         }
+        e = launch_scatter_sum(rec, n, k, d, (uint32_t *)c->ws_mat.ptr, &c->mat_clean,
+                               c->status + 16, coef, out, acc, status, s);
+        if (e != hipSuccess) c->mat_clean = 0;  // the emptying pass may not have run
+        break;
+    case kRouteCountingFold:
+        e = ordered_fold_records(c, rec, n * k, d, coef, out, acc, status, s);
+        break;
+    case kRouteFlatOrdered:
+    case kRouteSweep:
+        // baseline / path_oram on sparse uploads: the ordered sweep (exact for any
+        // upload, a client may repeat an index; fixed cost n*k*d compare-selects) —
+        // or, for dense-sized uploads (flat_ordered), the composite-key network's
+        // ordered fold (exact for any upload too).  Records with idx >= d are ignored
+        // (o_update's compare never matches): the network's range flag goes to a
+        // scratch word.
+        if (alg == FLTEE_ALG_PATH_ORAM)  // oram.rs: blocks beyond next_pow2(d) do not exist
+            e = launch_check_range(rec, n * k, (uint32_t)next_pow2_sz(d), status, s);
+        if (e == hipSuccess && p.route == kRouteFlatOrdered)
+            e = ordered_fold_records(c, rec, n * k, d, coef, out, acc, c->status + 32, s, true);
+        else if (e == hipSuccess)
+            e = launch_sweep_accumulate(rec, n * k, d, coef, out, acc, s);
+        break;
+    case kRouteAdvanced:
+    case kRouteBubble:  // alg 7: the stable sort, then advanced's fold / compaction / extract
+        e = run_advanced(c, rec, p.adv, coef, out, acc, status, s);
+        break;
+    case kRouteOptimized:
+        if (!acc) e = fl_memset_async(out, 0, d * 4, s);
+        for (size_t c0 = 0; e == hipSuccess && c0 < n; c0 += p.batch)
+            e = run_advanced(c, (const uint8_t *)rec + c0 * k * 8, c0 + p.batch <= n ? p.adv : p.adv_last,
+                             1.0f, out, true, status, s);
         if (e == hipSuccess && coef != 1.0f) e = launch_scale(out, d, coef, s);
         break;
-    }
-    case FLTEE_ALG_NIPS19: {
-        // nips19.rs:38 takes T and the Laplace scale from the REQUEST's
-        // num_of_sparse_parameters (0 for fl_main.py's dense uploads), not the payload
-        const size_t kq = (o.flags & FLTEE_OPT_K_REQ) ? o.k_req : k;
-        const float T = nips19_threshold(d, kq, n);
-        const size_t tf = f32_to_usize_sat(T);
-        const size_t L = n * k + d * tf, M = next_pow2_sz(L);
-        if (L >= ((size_t)1 << 31) || M > kMaxNet) return FLTEE_ERROR_INVALID_PARAMETER;
+    case kRouteNips19: {
         const uint64_t seed = o.seed ? o.seed : next_seed();
-        uint32_t *r = (uint32_t *)c->ws_r.ptr;
         uint64_t *A = (uint64_t *)c->ws_a.ptr;
-        e = launch_laplace_r(d, kq, T, seed, r, s);
+        const uint32_t *r = (const uint32_t *)c->ws_r.ptr;
+        e = launch_laplace_r(d, p.kq, p.T, seed, (uint32_t *)c->ws_r.ptr, s);
         const uint32_t key = (uint32_t)(seed ^ (seed >> 32));
         bool done = false;
-        if (e == hipSuccess && g_nips19_fused_select) {  // build + shuffle + select fused
-            e = nips19_shuffle_aggregate(c, A, M, key, rec, n * k, r, d, tf, coef, out, acc,
-                                         status, s);
+        if (e == hipSuccess && p.sel_tiles) {  // build + shuffle + select fused
+            e = nips19_shuffle_aggregate(c, p, key, rec, n * k, d, coef, out, acc, status, s);
             done = e != hipErrorNotSupported;
             if (!done) e = hipSuccess;
         }
         if (e == hipSuccess && !done) {  // build fused into the shuffle's first pass where it can be
-            e = bitonic_sort_nips19(A, M, key, rec, n * k, r, d, tf, s);
+            e = bitonic_sort_nips19(A, p.M, key, rec, n * k, r, d, p.tf, s);
             if (e == hipErrorNotSupported) {
-                e = launch_nips19_build(rec, n * k, r, d, tf, M, A, s);
-                if (e == hipSuccess) e = bitonic_sort(A, M, 2, key, s, L);
+                e = launch_nips19_build(rec, n * k, r, d, p.tf, p.M, A, s);
+                if (e == hipSuccess) e = bitonic_sort(A, p.M, 2, key, s, p.L);
             }
-            if (e == hipSuccess) e = safe_aggregate_ordered(c, A, M, d, coef, out, acc, status, s);
+            if (e == hipSuccess) e = safe_aggregate_ordered(c, A, p.M, d, coef, out, acc, status, s);
         }
         break;
     }
     default:
-        return FLTEE_ERROR_INVALID_PARAMETER;  // lib.rs:396 panics on unknown algs
+        return FLTEE_ERROR_INVALID_PARAMETER;  // (the plan refuses every shape without a route)
     }
     if (e == hipSuccess && (o.flags & FLTEE_OPT_DP)) {
         const uint64_t seed = o.seed ? o.seed : next_seed();
@@ -640,14 +628,37 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
 
 size_t workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
     const Plan p = plan_for(alg, n, k, d, o);
-    return p.a_bytes + p.b_bytes + p.mat_bytes + p.r_bytes + p.coef_bytes + p.rec_bytes +
-           p.keys_bytes + p.radix_bytes + p.oram_bytes + p.side_bytes + p.lb_bytes + p.s16_bytes;
+    size_t sum = 0;
+    for (size_t b : p.bytes) sum += b;
+    return sum;
 }
 
 bool reserve(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
     DeviceCtx *c = current_ctx();
-    return c && reserve_plan(c, plan_for(alg, n, k, d, o));
+    return c && reserve_plan(c, plan_for(alg, n, k, d, o), nullptr);
 }
+
+// fltee_debug_plan: the plan as words (host only, no device needed)
+fltee_status_t debug_plan_words(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o,
+                                uint64_t *out) {
+    const Plan p = plan_for(alg, n, k, d, o);
+    out[0] = p.route, out[1] = p.adv.tail;
+    out[2] = p.route == kRouteNips19 ? p.M : p.adv.M, out[3] = p.adv.halo;
+    for (int w = 0; w < kWsCount; ++w) out[4 + w] = p.bytes[w];
+    return p.status;
+}
+
+// fltee_debug_scratch_release: the current device's engine scratch freed, what described
+// its contents forgotten (the caller holds the API mutex)
+void release_scratch() {
+    DeviceCtx *c = current_ctx();
+    if (!c) return;
+    for (auto w : kScratch) (c->*w).release();
+    c->mat_clean = c->mat_clean_cap = 0;
+    c->mat_clean_ptr = nullptr;
+    c->fc_epoch = 0;
+}
+
 
 }  // namespace fltee
 
@@ -1088,6 +1099,28 @@ extern "C" void fltee_debug_set_aes_variant(int v) {
 }
 extern "C" void fltee_debug_set_swizzle(int on) { fltee::set_swizzle(on); }
 extern "C" void fltee_debug_set_fused_init(int on) { fltee::set_fused_init(on); }
+// test hook: the one decision aggregate() takes about a public shape (engine.h Plan), host
+// only: no device is touched.  Returns what fltee_aggregate_device returns for the shape
+// before it launches anything (FLTEE_SUCCESS or the 0x2 refusal) and writes 4 + kWsCount
+// words: out[0] the route (engine.h Route), out[1] the `advanced` family's tail (Tail; alg 6:
+// a full batch's), out[2] M (the sorted array: advanced / alg 7 / an alg-6 batch / the lazy
+// tree's readout / nips19; 0 otherwise), out[3] the effective fold halo, then the bytes of
+// each scratch buffer in Ws order (a, b, mat, r, coef, rec, keys, radix, oram, side, lb, s16,
+// cnt, sel) — their sum is fltee_workspace_bytes.  sel is always 0: nips19's selected list,
+// and the keys / radix its ordered fold takes, are sized from a count read back from the
+// device.  The sizes are filled in for a refused shape too.
+extern "C" fltee_status_t fltee_debug_plan(uint32_t alg, size_t n, size_t k, size_t d,
+                                           const fltee_device_opts *opts, uint64_t *out) {
+    return fltee::debug_plan_words(alg, n, k, d, opts ? *opts : default_opts(), out);
+}
+// test hooks: which engine scratch buffers grew (allocated) since the last call — bit w for
+// buffer w in Ws order — read and cleared; and the current device's engine scratch released
+// (with the scatter rows' clean mark and the look-back epoch), so a test can start from empty.
+extern "C" uint32_t fltee_debug_scratch_grown(void) { return fltee::g_scratch_grown.exchange(0); }
+extern "C" void fltee_debug_scratch_release(void) {
+    std::lock_guard<std::recursive_mutex> lk(fltee::api_mutex());
+    fltee::release_scratch();
+}
 // test hook: how run_advanced folds a whole array of L = n * k + d entries (M = next_pow2(L),
 // fold_len == L, halo = the effective one: opts.fold_halo, or n) under the current A/B
 // settings.  Read-only, host only.  out[0]: 1 the fold fused into the compaction's first

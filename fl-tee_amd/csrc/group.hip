@@ -568,7 +568,7 @@ uint32_t group_advanced(Group *Gp, const GroupInput &in, size_t n, size_t k, siz
     Group &G = *Gp;
     const int W = G.W;
     const size_t nrec = n * k, L = nrec + d, M = next_pow2_sz(L), C = M / W;
-    if (C < (size_t)W * 16 || M > ((size_t)1 << 29)) return FLTEE_GROUP_FALLBACK;
+    if (C < (size_t)W * 16 || M > kMaxNetRecords) return FLTEE_GROUP_FALLBACK;
     std::vector<uint64_t *> chunk, spare;
     if (!reserve_chunks(G, C, chunk, spare)) return FLTEE_ERROR_OUT_OF_MEMORY;
     std::vector<size_t> lo(W), hi(W);
@@ -658,7 +658,7 @@ uint32_t group_nips19(Group *Gp, DeviceCtx *root, const GroupInput &in, size_t n
     const float T = nips19_threshold(d, k_req, n);
     const size_t tf = !(T > 0.0f) ? 0 : (size_t)T;
     const size_t nrec = n * k, L = nrec + d * tf, M = next_pow2_sz(L), C = M / W;
-    if (C < 64 || M > ((size_t)1 << 29) || d == 0) return FLTEE_GROUP_FALLBACK;
+    if (C < 64 || M > kMaxNetRecords || d == 0) return FLTEE_GROUP_FALLBACK;
     const uint32_t key = (uint32_t)(seed ^ (seed >> 32));  // the shuffle key of aggregate()
     std::vector<uint64_t *> chunk, spare;
     if (!reserve_chunks(G, C, chunk, spare)) return FLTEE_ERROR_OUT_OF_MEMORY;

@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256) void stable_tile_merge_kernel(uint4 *__restric
     st_tile_out(tile, t, pbase, m, data, out8);
 }
 
-size_t stable_sort_max_records() { return (size_t)1 << 29; }
+size_t stable_sort_max_records() { return kMaxNetRecords; }
 
 // live records of a pass over stage blocks of 2^stage: the blocks that start below valid
 static uint64_t st_live(size_t m, size_t valid, uint32_t stage) {

@@ -122,6 +122,9 @@ EXTRA_SIGNATURES = {  # test hooks not in the public header
     "fltee_debug_net_log": (_S, [_S, ctypes.c_char_p, _S, _P, _P]),
     "fltee_debug_set_fold_compact": (None, [ctypes.c_int]),
     "fltee_debug_fold_geometry": (None, [_S, _S, _S, _S, _P]),
+    "fltee_debug_plan": (_U32, [_U32, _S, _S, _S, ctypes.POINTER(DeviceOpts), _P]),
+    "fltee_debug_scratch_grown": (_U32, []),
+    "fltee_debug_scratch_release": (None, []),
     "fltee_debug_set_pad_skip": (None, [ctypes.c_int]),
     "fltee_debug_set_radix_order": (None, [ctypes.c_int]),
     "fltee_debug_set_swizzle": (None, [ctypes.c_int]),

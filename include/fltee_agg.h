@@ -204,10 +204,18 @@ fltee_status_t fltee_aggregate_device(uint32_t alg, const void *d_records, size_
                                       size_t d, float *d_out, const fltee_device_opts *opts,
                                       void *stream);
 
-/* Bytes of scratch HBM the library will hold for this shape (grow-only). */
+/* Bytes of scratch HBM the library will hold for this shape (grow-only): the sum over
+ * every scratch buffer the call touches, from the same shape plan the call itself runs
+ * by.  Not counted, because it depends on the data: nips19's selected list (8 bytes per
+ * entry that survives the threshold, and the sort scratch of its ordered fold), sized
+ * from a count read back from the device. */
 size_t fltee_workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d,
                              const fltee_device_opts *opts);
-/* Pre-size the scratch so the first timed call does no hipMalloc. */
+/* Pre-size that scratch: a later fltee_aggregate_device of the same shape and options
+ * (and of any shape needing no more of each buffer) allocates and frees nothing — no
+ * hipMalloc, and no hipFree with its device-wide synchronisation, inside a timed call.
+ * The one exception is nips19's selected list above, which grows with the largest
+ * count seen. */
 fltee_status_t fltee_reserve(uint32_t alg, size_t n, size_t k, size_t d,
                              const fltee_device_opts *opts);
 
