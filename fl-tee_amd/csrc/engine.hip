@@ -242,11 +242,6 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
     auto refuse_if = [&p](bool bad) { if (bad) p.status = FLTEE_ERROR_INVALID_PARAMETER; };
     // 32-bit positions; a dense upload has one record per parameter
     refuse_if(n == 0 || nrec + d >= ((size_t)1 << 31) || (dense && k != d));
-    if (o.flags & FLTEE_OPT_CLIP) {
-        p.bytes[kWsCoef] = n * 4;
-        p.clip_records = !dense || tree;  // the tree reads records
-        if (p.clip_records) p.bytes[kWsRec] = nrec * 8;
-    }
     switch (alg) {
     case FLTEE_ALG_PATH_ORAM:
     case FLTEE_ALG_BASELINE:
@@ -320,6 +315,13 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
     default:
         refuse_if(true);  // lib.rs:396 panics on unknown algs
         break;
+    }
+    if (o.flags & FLTEE_OPT_CLIP) {
+        // every route but the dense accumulate (which takes the coefficients) reads records:
+        // FLTEE_OPT_DENSE on algs 1, 2, 6, 7 and on the tree only asserts k == d
+        p.bytes[kWsCoef] = n * 4;
+        p.clip_records = p.route != kRouteDense;
+        if (p.clip_records) p.bytes[kWsRec] = nrec * 8;
     }
     return p;
 }
@@ -589,7 +591,8 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
         for (size_t c0 = 0; e == hipSuccess && c0 < n; c0 += p.batch)
             e = run_advanced(c, (const uint8_t *)rec + c0 * k * 8, c0 + p.batch <= n ? p.adv : p.adv_last,
                              1.0f, out, true, status, s);
-        if (e == hipSuccess && coef != 1.0f) e = launch_scale(out, d, coef, s);
+        // accumulate: out += sum, un-averaged as on every other route (what was in out stays)
+        if (e == hipSuccess && !acc && coef != 1.0f) e = launch_scale(out, d, coef, s);
         break;
     case kRouteNips19: {
         const uint64_t seed = o.seed ? o.seed : next_seed();

@@ -164,10 +164,19 @@ fltee_status_t ecall_client_size_optimized_secure_aggregation(
 #define FLTEE_DEV_ERR_LAUNCH 0x80000000u
 
 /* option flags */
-#define FLTEE_OPT_DENSE 0x1u      /* records are dense: client c, slot j has idx j */
-#define FLTEE_OPT_DP 0x2u         /* add N(0, clipping*sigma)/n noise (common.rs:56-72) */
-#define FLTEE_OPT_CLIP 0x4u       /* server-side per-client L2 clip (update.py:187-204) */
-#define FLTEE_OPT_ACCUMULATE 0x8u /* out += sum (no averaging): alg-6 batches, shards */
+#define FLTEE_OPT_DENSE 0x1u      /* records are dense: client c, slot j has idx j (k == d, else
+                                     INVALID_PARAMETER).  Algs 3, 4, 5 take the dense
+                                     accumulate; on algs 1, 2, 6, 7 and the tree it changes
+                                     nothing else */
+#define FLTEE_OPT_DP 0x2u         /* add N(0, clipping*sigma)/n_avg noise (common.rs:56-72), one
+                                     f32 add per parameter after everything else */
+#define FLTEE_OPT_CLIP 0x4u       /* server-side per-client L2 clip (update.py:187-204) in front
+                                     of every alg and route, whatever FLTEE_OPT_DENSE says:
+                                     v * min(1, f32(C) / f32(sqrt(f64 sum of v^2))) in f32, on a
+                                     scratch copy (d_records is never written) */
+#define FLTEE_OPT_ACCUMULATE 0x8u /* out += sum, on every alg and route: the sum is never
+                                     averaged (FLTEE_OPT_NO_AVERAGE and n_avg are ignored) and
+                                     what d_out held is never scaled: alg-6 batches, shards */
 #define FLTEE_OPT_NO_AVERAGE 0x10u /* skip the 1/n scaling (partial sums for RCCL) */
 #define FLTEE_OPT_K_REQ 0x20u      /* advanced: fold over n*k_req+d even if k_req != k
                                       (advanced.rs:70 uses the REQUEST's k; 0 when
@@ -189,7 +198,8 @@ typedef struct fltee_device_opts {
     uint64_t seed;      /* RNG seed for nips19 / DP; 0 = draw from getrandom() */
     size_t k_req;       /* advanced: request num_of_sparse_parameters (with FLTEE_OPT_K_REQ) */
     size_t batch;       /* alg 6: optimal_num_of_clients */
-    size_t n_avg;       /* divisor for averaging (0 = n) */
+    size_t n_avg;       /* divisor for averaging (0 = n): out = sum * (1f32 / (f32)n_avg), and
+                           the DP noise's divisor */
     size_t fold_halo;   /* advanced fold halo H (0 = n): runs of <= H + 1 entries (each client's
                            indices distinct) bit for bit, longer ones re-associated at the
                            fold's walk boundaries */

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, gpu_available
+from options_model import clip_model as _clip_model
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
@@ -41,20 +42,6 @@ def _bytes(t):
 
 def _vals(b):
     return b.reshape(-1, 8)[:, 4:].copy().view("<f4").ravel()
-
-
-def _clip_model(vals, n, clipping):
-    """update.py:187-204 with an exactly rounded norm: norm32 = f32(sqrt(sum v^2)) (f64
-    sum), coef = min(1, f32(C / norm32)), v * coef in f32 — torch's arithmetic, minus
-    the fp32 accumulation error of torch.norm (relative ~sqrt(d) * 2^-24: ~1e-6 at
-    d = 5e4), which is why the reference itself is compared within 2e-6."""
-    out = []
-    for v in vals.reshape(n, -1):
-        norm32 = np.float32(np.sqrt(np.sum(v.astype(np.float64) ** 2)))
-        cf = np.float32(np.float32(clipping) / norm32)
-        cf = cf if cf < 1 else np.float32(1)
-        out.append((v * cf).astype(np.float32))
-    return np.concatenate(out)
 
 
 def test_topk_serialize_matches_reference(C, fx):

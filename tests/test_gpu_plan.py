@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 from conftest import gpu_available
-from stable_model import bits_equal, distinct_indices, model
+from options_model import reference
+from stable_model import bits_equal, distinct_indices
 from test_plan import CLIPPED, ROUTES, WS
 
 pytestmark = [pytest.mark.gpu,
@@ -36,24 +37,6 @@ def upload(alg, n, k, d, dense):
     else:
         idx = distinct_indices(rng, n, k, d)
     return idx, rng.normal(0, 0.01, n * k).astype(np.float32)
-
-
-def reference(oracle, alg, idx, val, n, k, d, kw):
-    w = oracle.as_weights(idx, val)
-    if alg == 1:
-        ref, st = oracle.advanced(kw.get("k_req", k), w, d, n)
-    elif alg == 2:
-        ref, st = oracle.nips19(k, w, d, n, seed=kw["seed"])
-    elif alg == 6:
-        ref, st = oracle.client_size_optimized(kw["batch"], k, w, d, n)
-    elif alg == 7:
-        ref, st = model(idx, val, n, d), 0
-    elif alg == 3:
-        ref, st = oracle.baseline(w, d, n), 0
-    else:
-        ref, st = {4: oracle.non_oblivious, 5: oracle.path_oram}[alg](w, d, n)
-    assert st == 0
-    return ref
 
 
 def reserved_run(dev, alg, rec, n, k, d, kw):

@@ -69,12 +69,58 @@ CLIPPED = [
 ]
 
 
-@pytest.mark.parametrize("case", ROUTES + CLIPPED, ids=lambda c: c[0])
+def option_shapes():
+    """The option tests' table (tests/test_gpu_options.py): the fourteen routes at shapes the
+    lattice inputs of tests/options_model.py fit (k >= 16 wherever the route has records,
+    n = 6 where that is free so that every lattice client occurs), and the dense-flagged
+    uploads (k == d) of the algs that have no dense route."""
+    change = {
+        "dense": dict(n=6),
+        "scatter rows": dict(n=6, k=16),
+        "counting-sort fold": dict(k=16),
+        "sweep": dict(n=6, k=16),
+        "flat-ordered": dict(n=6),
+        "tree": dict(n=6, k=16, d=32),
+        "tree lazy": dict(n=6, k=16, d=32),
+        "advanced second sort": dict(k=16),  # (n stays 4: see test_gpu_options.py sums)
+        "nips19": dict(n=6),
+    }
+    out = []
+    for name, alg, n, k, d, kw, route, tail in ROUTES:
+        c = change.get(name, {})
+        out.append((name + ", options", alg, c.get("n", n), c.get("k", k), c.get("d", d), kw, route, tail))
+    return out + [
+        ("advanced, dense flag", 1, 7, 64, 64, dict(dense=True), R_ADVANCED, T_FUSED),
+        ("nips19, dense flag", 2, 7, 64, 64, dict(dense=True, seed=7), R_NIPS19, T_NONE),
+        ("alg 6, dense flag", 6, 7, 64, 64, dict(dense=True, batch=3), R_OPTIMIZED, T_FUSED),
+        ("alg 7, dense flag", 7, 7, 64, 64, dict(dense=True), R_BUBBLE, T_FUSED),
+    ]
+
+
+OPTION_SHAPES = option_shapes()
+
+
+@pytest.mark.parametrize("case", ROUTES + CLIPPED + OPTION_SHAPES, ids=lambda c: c[0])
 def test_routes_and_tails(case):
     _, alg, n, k, d, kw, route, tail = case
     p = Plan(alg, n, k, d, **kw)
     assert p.status == 0
     assert (p.route, p.tail) == (route, tail)
+
+
+@pytest.mark.parametrize("case", ROUTES + OPTION_SHAPES, ids=lambda c: c[0])
+def test_clip_scratch_of_every_route(case):
+    """FLTEE_OPT_CLIP changes no route; a coefficient per client everywhere, and a clipped
+    copy of the records on every route but the dense accumulate of algs 3, 4 and 5 (which
+    takes the coefficients) — FLTEE_OPT_DENSE on algs 1, 2, 6 and 7 only asserts k == d."""
+    _, alg, n, k, d, kw, route, tail = case
+    plain, p = Plan(alg, n, k, d, **kw), Plan(alg, n, k, d, clip=True, clipping=0.5, **kw)
+    assert p.status == 0 and (p.route, p.tail) == (route, tail)
+    assert p.bytes["coef"] == n * 4
+    assert p.bytes["rec"] == (0 if route == R_DENSE else n * k * 8)
+    assert plain.bytes["coef"] == 0 and plain.bytes["rec"] == 0
+    assert {w: b for w, b in p.bytes.items() if w not in ("coef", "rec")} == \
+           {w: b for w, b in plain.bytes.items() if w not in ("coef", "rec")}
 
 
 def nips19_kq(d, n, tf):
@@ -153,6 +199,9 @@ def test_nips19_tf_overflow_is_refused():
     ("advanced, a wide halo", 1, 2, 3, 40, dict(fold_halo=100), R_ADVANCED, None),
     ("alg 6, one batch", 6, 10, 50, 500, {}, R_OPTIMIZED, None),
     ("nips19 with dummies", 2, 30, 500, 5000, dict(k_req=16), R_NIPS19, None),
+] + OPTION_SHAPES + [
+    (name + ", clip", alg, n, k, d, dict(kw, clip=True, clipping=0.5), route, tail)
+    for name, alg, n, k, d, kw, route, tail in OPTION_SHAPES
 ], ids=lambda c: c[0])
 def test_workspace_bytes_is_the_sum_of_the_plan(case):
     from fltee import device as D
@@ -221,6 +270,8 @@ def test_clip_scratch():
     assert Plan(4, 4, 8, 100, clip=True).bytes["rec"] == 4 * 8 * 8
     assert Plan(3, 3, 257, 257, dense=True, clip=True).bytes["rec"] == 0
     assert Plan(5, 2, 16, 16, dense=True, clip=True, oram_tree=True).bytes["rec"] == 2 * 16 * 8
+    for alg, kw in ((1, {}), (2, dict(seed=7)), (6, dict(batch=3)), (7, {})):  # no dense route
+        assert Plan(alg, 4, 64, 64, dense=True, clip=True, **kw).bytes["rec"] == 4 * 64 * 8
     assert Plan(0, 4, 8, 100, clip=True).status == INVALID
 
 
