@@ -211,6 +211,24 @@ size_t stable_sort_max_records();
 hipError_t stable_sort(void *data16, size_t m, hipStream_t s, size_t valid = 0, bool init = false,
                        const void *rec = nullptr, size_t nrec = 0, size_t d = 0,
                        uint64_t *out8 = nullptr);
+// One range of a position-sharded array: data16[0, m) holds the global positions [pos_base,
+// pos_base + m), pos_base a multiple of m = 2^j >= 2^12, pos_base + m <= 2^31 (group.hip;
+// the fltee_stable_*_device pieces).  Every direction comes from the global position.
+// sort_range: stages 1..log2 m (stable_sort is pos_base = 0 over the whole array; valid in
+// local positions; with init, rec points at the record of position pos_base).  merge_range:
+// the steps m/2..1 of stage 2^stage > m.  exchange: the step |pos_mine - pos_theirs| >= m of
+// stage 2^stage against a copy of the partner range.  init_range: the range's entries on
+// their own.  strip_range: 16-byte records -> the fold's 8-byte (idx, val).
+hipError_t stable_sort_range(void *data16, size_t m, size_t pos_base, hipStream_t s, size_t valid = 0,
+                             bool init = false, const void *rec = nullptr, size_t nrec = 0,
+                             size_t d = 0, uint64_t *out8 = nullptr);
+hipError_t stable_merge_range(void *data16, size_t m, size_t pos_base, uint32_t stage, hipStream_t s,
+                              uint64_t *out8 = nullptr);
+hipError_t stable_exchange(void *mine16, const void *theirs16, size_t m, size_t pos_mine,
+                           size_t pos_theirs, uint32_t stage, hipStream_t s);
+hipError_t stable_init_range(const void *rec, size_t nrec, size_t d, size_t pos_base, size_t m,
+                             void *dst16, hipStream_t s);
+hipError_t stable_strip_range(const void *data16, size_t m, uint64_t *dst8, hipStream_t s);
 
 // k_fold.hip
 hipError_t launch_advanced_init(const void *rec, size_t nrec, size_t d, size_t m, uint64_t *dst,

@@ -538,8 +538,10 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         if (st != FLTEE_SUCCESS && st != FLTEE_GROUP_FALLBACK) return fail(st);
     }
     // (the exact-runs policy folds on one GPU: one sequential walk of the sorted array)
-    const bool sharded = G && ((aggregation_alg == FLTEE_ALG_ADVANCED && k_req == rpc &&
-                                !exact_runs_default()) ||
+    // (alg 7, once the host has opted in, shards like advanced: the same fold and tail)
+    const bool sharded = G && (((aggregation_alg == FLTEE_ALG_ADVANCED ||
+                                 (aggregation_alg == FLTEE_ALG_BUBBLE && bubble_ecall_default())) &&
+                                k_req == rpc && !exact_runs_default()) ||
                                aggregation_alg == FLTEE_ALG_NIPS19);
     // nips19 draws its seed (Laplace counts, shuffle key) once per call, whichever path
     // runs it, so a multi-GPU eid consumes the seed sequence exactly as one GPU does
@@ -558,6 +560,8 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         const double ta = now_s();
         if (aggregation_alg == FLTEE_ALG_ADVANCED)
             st = group_advanced(G, in, n, rpc, d, coef, d_out);
+        else if (aggregation_alg == FLTEE_ALG_BUBBLE)
+            st = group_bubble(G, in, n, rpc, d, coef, d_out);
         else
             st = group_nips19(G, c, in, n, rpc, k_req, d, seed, coef, d_out);
         group_tried = true;
@@ -592,6 +596,8 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         if (sharded && !group_tried) {
             if (aggregation_alg == FLTEE_ALG_ADVANCED)
                 st = group_advanced(G, in, n, rpc, d, coef, d_out);
+            else if (aggregation_alg == FLTEE_ALG_BUBBLE)
+                st = group_bubble(G, in, n, rpc, d, coef, d_out);
             else
                 st = group_nips19(G, c, in, n, rpc, k_req, d, seed, coef, d_out);
         }

@@ -830,6 +830,68 @@ extern "C" fltee_status_t fltee_bitonic_range_steps_device(void *d_records, size
                : FLTEE_ERROR_UNEXPECTED;
 }
 
+// ---- position-range pieces of alg 7's stable network (k_stable.hip) -------
+// host arithmetic only: every refusal comes before any HIP call
+static bool stable_range_ok(size_t m, size_t pos_base) {
+    return m >= ((size_t)1 << 12) && m <= ((size_t)1 << 29) && !(m & (m - 1)) && pos_base % m == 0 &&
+           pos_base <= ((size_t)1 << 31) && pos_base + m <= ((size_t)1 << 31);
+}
+
+extern "C" fltee_status_t fltee_stable_init_range_device(const void *d_records, size_t nrec, size_t d,
+                                                         size_t pos_base, size_t m, void *d_dst16,
+                                                         void *stream) {
+    if (!stable_range_ok(m, pos_base) || nrec >= ((size_t)1 << 31) || d >= ((size_t)1 << 31) ||
+        nrec + d >= ((size_t)1 << 31))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    return stable_init_range(d_records, nrec, d, pos_base, m, d_dst16, (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_stable_range_sort_device(void *d_rec16, size_t m, size_t pos_base,
+                                                         size_t valid, void *stream) {
+    if (!stable_range_ok(m, pos_base)) return FLTEE_ERROR_INVALID_PARAMETER;
+    if (valid == 0) return FLTEE_SUCCESS;  // pads alone: sorted as they are
+    return stable_sort_range(d_rec16, m, pos_base, (hipStream_t)stream, valid >= m ? 0 : valid) ==
+                   hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_stable_range_exchange_device(void *d_mine16, const void *d_theirs16,
+                                                             size_t m, size_t pos_mine,
+                                                             size_t pos_theirs, uint32_t stage_log,
+                                                             void *stream) {
+    if (!stable_range_ok(m, pos_mine) || !stable_range_ok(m, pos_theirs) || pos_mine == pos_theirs ||
+        stage_log > 31)
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    const size_t j = pos_mine > pos_theirs ? pos_mine - pos_theirs : pos_theirs - pos_mine;
+    // a power of two below the stage; the partner differs in that one position bit
+    if ((j & (j - 1)) || j >= ((size_t)1 << stage_log) || (pos_mine ^ pos_theirs) != j)
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    return stable_exchange(d_mine16, d_theirs16, m, pos_mine, pos_theirs, stage_log,
+                           (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_stable_range_merge_device(void *d_rec16, size_t m, size_t pos_base,
+                                                          uint32_t stage_log, void *stream) {
+    if (!stable_range_ok(m, pos_base) || stage_log > 31 || ((size_t)1 << stage_log) <= m)
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    return stable_merge_range(d_rec16, m, pos_base, stage_log, (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_stable_range_strip_device(const void *d_rec16, size_t m, void *d_dst8,
+                                                          void *stream) {
+    if (!stable_range_ok(m, 0)) return FLTEE_ERROR_INVALID_PARAMETER;
+    return stable_strip_range(d_rec16, m, (uint64_t *)d_dst8, (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
 extern "C" size_t fltee_fold_context(size_t halo) { return fold_context(halo); }
 
 extern "C" size_t fltee_fold_side_bytes(size_t span, size_t halo) {

@@ -36,6 +36,10 @@ struct GroupInput {
 };
 uint32_t group_advanced(Group *G, const GroupInput &in, size_t n, size_t k, size_t d, float coef,
                         float *d_out_root);
+// alg 7 (k fold entries per client = the request's k): the stable network of k_stable.hip
+// over position ranges (pairwise exchanges), then group_advanced's tail
+uint32_t group_bubble(Group *G, const GroupInput &in, size_t n, size_t k, size_t d, float coef,
+                      float *d_out_root);
 uint32_t group_nips19(Group *G, DeviceCtx *root, const GroupInput &in, size_t n, size_t k,
                       size_t k_req, size_t d, uint64_t seed, float coef, float *d_out_root);
 // halo: the fold halo of every batch (n, or the exact-runs policy's worst case)

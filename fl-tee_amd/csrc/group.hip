@@ -22,6 +22,10 @@
 //     range exchanges: the comparator reads the position); each range selects its
 //     entries with idx < d in order, the lists are gathered to the root in range order
 //     (= the global shuffled order) and the root runs the ordered fold.  Bit-identical.
+//   bubble (alg 7): POSITION-RANGE sharding like advanced, on the 16-byte records of the
+//     stable network (k_stable.hip): range sorts, pairwise range exchanges (partner
+//     r ^ j/C per cross-range step), range merges; the stripped ranges then take
+//     advanced's halo fold, long-run patch, compaction and reduce.  Bit-identical.
 //   optimized (alg 6): the batches are split over the GPUs; each GPU's batch sums are
 //     sent to the root as rows, which adds them in batch order (lib.rs:564-573).
 //     Bit-identical to one GPU.
@@ -375,9 +379,15 @@ static uint32_t group_records(Group &G, const GroupInput &in, size_t n, size_t r
             fl_stream_sync(R.s) != hipSuccess)
             errs[i] = 1;
     };
+    // one host thread per GPU (as group_dense_ecall); ranks on one device share a stream:
+    // they load in rank order, which also keeps the launch trace's order a fixed one
     std::vector<std::thread> th;
-    for (int i = 0; i < W; ++i) th.emplace_back(load, i);
-    for (auto &t : th) t.join();
+    if (G.rccl && W > 1) {
+        for (int i = 0; i < W; ++i) th.emplace_back(load, i);
+        for (auto &t : th) t.join();
+    } else {
+        for (int i = 0; i < W; ++i) load(i);
+    }
     for (int i = 0; i < W; ++i)
         if (errs[i]) return errs[i] == 3 ? FLTEE_ERROR_OUT_OF_MEMORY : FLTEE_ERROR_UNEXPECTED;
     const auto t1 = std::chrono::steady_clock::now();
@@ -549,13 +559,14 @@ static hipError_t network(Group &G, std::vector<uint64_t *> &chunk, std::vector<
     return hipSuccess;
 }
 
+// every rank's range and its spare: C records of rec_bytes (8; alg 7's network: 16)
 static bool reserve_chunks(Group &G, size_t C, std::vector<uint64_t *> &chunk,
-                           std::vector<uint64_t *> &spare) {
+                           std::vector<uint64_t *> &spare, size_t rec_bytes = 8) {
     chunk.assign(G.W, nullptr);
     spare.assign(G.W, nullptr);
     for (int i = 0; i < G.W; ++i) {
         Rank &R = G.r[i];
-        if (!reserve_on(R, R.chunk, C * 8) || !reserve_on(R, R.spare, C * 8)) return false;
+        if (!reserve_on(R, R.chunk, C * rec_bytes) || !reserve_on(R, R.spare, C * rec_bytes)) return false;
         chunk[i] = (uint64_t *)R.chunk.ptr;
         spare[i] = (uint64_t *)R.spare.ptr;
     }
@@ -563,6 +574,9 @@ static bool reserve_chunks(Group &G, size_t C, std::vector<uint64_t *> &chunk,
 }
 
 // ============================================================= advanced =====
+static uint32_t sorted_ranges_tail(Group &G, const std::vector<uint64_t *> &chunk, size_t C, size_t L,
+                                   size_t n, size_t d, float coef, float *d_out_root);
+
 uint32_t group_advanced(Group *Gp, const GroupInput &in, size_t n, size_t k, size_t d,
                         float coef, float *d_out_root) {
     Group &G = *Gp;
@@ -581,10 +595,19 @@ uint32_t group_advanced(Group *Gp, const GroupInput &in, size_t n, size_t k, siz
             return FLTEE_ERROR_UNEXPECTED;
     }
     if (network(G, chunk, spare, M, 0, 0, W > 1, n * k + d) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
-    // fold (advanced.rs:66-101) with the previous range's tail in front (the halo and the
-    // record before it) and the next range's head behind, halo n; then the long-run patch
-    // (k_fold.hip): every range's segmented total goes to the ranges after it (device to
-    // device), which finish the runs begun before them.  Fixed cost: no status readback.
+    return sorted_ranges_tail(G, chunk, C, L, n, d, coef, d_out_root);
+}
+
+// What follows the sort, for `advanced` and for alg 7 alike: chunk[i] = range i (C 8-byte
+// records) of the array sorted by idx, L = n * k + d its fold length, n the halo.
+// The fold (advanced.rs:66-101) with the previous range's tail in front (the halo and the
+// record before it) and the next range's head behind, halo n; then the long-run patch
+// (k_fold.hip): every range's segmented total goes to the ranges after it (device to
+// device), which finish the runs begun before them.  Fixed cost: no status readback.
+// Then each range's compacted representatives, one reduce to the root, the scale.
+static uint32_t sorted_ranges_tail(Group &G, const std::vector<uint64_t *> &chunk, size_t C, size_t L,
+                                   size_t n, size_t d, float coef, float *d_out_root) {
+    const int W = G.W;
     const size_t fold_len = L;
     const size_t h = n;
     const size_t X = fold_context(h) + 16;  // context records in front of each range
@@ -648,6 +671,69 @@ uint32_t group_advanced(Group *Gp, const GroupInput &in, size_t n, size_t k, siz
         (coef != 1.0f && launch_scale(d_out_root, d, coef, G.r[0].s) != hipSuccess))
         return FLTEE_ERROR_UNEXPECTED;
     return sync_all(G) == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+}
+
+// ================================================================ alg 7 =====
+// bubble_sort_based.rs over position ranges: the stable network of k_stable.hip on 16-byte
+// records keyed (idx << 32 | position), distributed as network() above is in its pairwise
+// form — range sorts (init fused into their loads), per stage 2^s > C the exchanges with
+// partner r ^ (2^j / C) for j = s - 1 .. log2 C, then the range merge (the last one's
+// stores strip the records to the fold's 8 bytes) — with network()'s pad rule: a range of
+// pads alone is only written, a stage skips the ranges at or past roundup(L, 2^stage).
+// Then advanced's tail.  The in-order client sum, bit for bit as on one GPU.
+uint32_t group_bubble(Group *Gp, const GroupInput &in, size_t n, size_t k, size_t d, float coef,
+                      float *d_out_root) {
+    Group &G = *Gp;
+    const int W = G.W;
+    const size_t nrec = n * k, L = nrec + d, M = next_pow2_sz(L), C = M / W;
+    if (C < ((size_t)1 << 12) || C < (size_t)W * 16 || fold_context(n) + 16 > C ||
+        M > kMaxNetRecords || M > stable_sort_max_records())
+        return FLTEE_GROUP_FALLBACK;
+    const uint32_t clog = log2_pow2(C), mlog = log2_pow2(M);
+    std::vector<uint64_t *> chunk, spare;
+    if (!reserve_chunks(G, C, chunk, spare, 16)) return FLTEE_ERROR_OUT_OF_MEMORY;
+    std::vector<size_t> lo(W), hi(W);
+    for (int i = 0; i < W; ++i) lo[i] = i * C, hi[i] = (i + 1) * C;
+    std::vector<const uint64_t *> rec;
+    if (uint32_t st = group_records(G, in, n, k, lo, hi, rec)) return st;
+    auto live_from = [&](uint32_t stage) -> size_t {  // ranges r with r*C >= this are pads alone
+        const size_t blk = (size_t)1 << stage;
+        const size_t b = (L + blk - 1) / blk * blk;
+        return b >= M ? M : b;
+    };
+    for (int i = 0; i < W; ++i) {
+        Rank &R = G.r[i];
+        if (hipSetDevice(R.dev) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+        const hipError_t e =
+            lo[i] >= L ? stable_init_range(rec[i], nrec, d, lo[i], C, chunk[i], R.s)  // pads alone
+                       : stable_sort_range(chunk[i], C, lo[i], R.s, L - lo[i] >= C ? 0 : L - lo[i], true,
+                                           rec[i], nrec, d, W == 1 ? spare[i] : nullptr);
+        if (e != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+    }
+    for (uint32_t stage = clog + 1; stage <= mlog; ++stage) {
+        const size_t sf = live_from(stage);
+        for (int j = (int)stage - 1; j >= (int)clog; --j) {
+            const int bit = 1 << (j - (int)clog);
+            std::vector<P2P> ops;
+            for (int r = 0; r < W; ++r)
+                if ((size_t)r * C < sf) ops.push_back({r ^ bit, r, chunk[r ^ bit], spare[r], C * 16});
+            if (p2p(G, ops) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+            for (int r = 0; r < W; ++r) {
+                if ((size_t)r * C >= sf) continue;
+                if (hipSetDevice(G.r[r].dev) != hipSuccess ||
+                    stable_exchange(chunk[r], spare[r], C, lo[r], lo[r ^ bit], stage, G.r[r].s) != hipSuccess)
+                    return FLTEE_ERROR_UNEXPECTED;
+            }
+        }
+        for (int i = 0; i < W; ++i) {  // (the last stage: sf = M, every range strips)
+            if ((size_t)i * C >= sf) continue;
+            if (hipSetDevice(G.r[i].dev) != hipSuccess ||
+                stable_merge_range(chunk[i], C, lo[i], stage, G.r[i].s,
+                                   stage == mlog ? spare[i] : nullptr) != hipSuccess)
+                return FLTEE_ERROR_UNEXPECTED;
+        }
+    }
+    return sorted_ranges_tail(G, spare, C, L, n, d, coef, d_out_root);  // the stripped ranges
 }
 
 // =============================================================== nips19 =====

@@ -86,6 +86,11 @@ SIGNATURES = {
     "fltee_bitonic_range_merge_device": (_U32, [_P, _S, _S, _U32, _U32, _U32, _P]),
     "fltee_bitonic_range_exchange_device": (_U32, [_P, _P, _S, _S, _S, _U32, _U32, _U32, _P]),
     "fltee_bitonic_range_steps_device": (_U32, [_P, _S, _S, _U32, _U32, _U32, _U32, _U32, _P]),
+    "fltee_stable_init_range_device": (_U32, [_P, _S, _S, _S, _S, _P, _P]),
+    "fltee_stable_range_sort_device": (_U32, [_P, _S, _S, _S, _P]),
+    "fltee_stable_range_exchange_device": (_U32, [_P, _P, _S, _S, _S, _U32, _P]),
+    "fltee_stable_range_merge_device": (_U32, [_P, _S, _S, _U32, _P]),
+    "fltee_stable_range_strip_device": (_U32, [_P, _S, _P, _P]),
     "fltee_fold_context": (_S, [_S]),
     "fltee_fold_side_bytes": (_S, [_S, _S]),
     "fltee_fold_range_device": (_U32, [_P, _P, _S, _S, _S, ctypes.c_int64, _S, _S, _P, _P]),

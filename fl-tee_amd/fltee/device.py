@@ -244,6 +244,61 @@ def compact_range(chunk, d, coef, buf, tmp, out=None, stream=None):
     return out
 
 
+# ---- position-range pieces of alg 7's stable network (fltee/parallel.py) ----
+def _records16(t):
+    """m of a tensor whose bytes are m 16-byte records (e.g. int64 [m, 2])"""
+    nbytes = t.numel() * t.element_size()
+    assert t.is_cuda and t.is_contiguous() and nbytes % 16 == 0
+    return nbytes // 16
+
+
+def stable_init_range(records, nrec, d, pos_base, m, out=None, stream=None):
+    """Entries pos_base..pos_base+m-1 of alg 7's padded array as 16-byte records (int64
+    [m, 2]: key = idx << 32 | global position; val bits); records[x] is the record at
+    position pos_base + x (read where < nrec)."""
+    if out is None:
+        out = torch.empty((m, 2), dtype=torch.int64, device=records.device)
+    _check(L.lib().fltee_stable_init_range_device(_ptr(records), nrec, d, pos_base, m, _ptr(out),
+                                                  _stream(stream)),
+           "fltee_stable_init_range_device")
+    return out
+
+
+def stable_range_sort(rec16, pos_base, valid=None, stream=None):
+    """Stages 1..log2 m on one range; valid: entries valid.. of it are pads (None: none)."""
+    m = _records16(rec16)
+    _check(L.lib().fltee_stable_range_sort_device(_ptr(rec16), m, pos_base,
+                                                  m if valid is None else valid, _stream(stream)),
+           "fltee_stable_range_sort_device")
+    return rec16
+
+
+def stable_range_exchange(mine16, theirs16, pos_mine, pos_theirs, stage_log, stream=None):
+    m = _records16(mine16)
+    assert _records16(theirs16) == m
+    _check(L.lib().fltee_stable_range_exchange_device(_ptr(mine16), _ptr(theirs16), m, pos_mine,
+                                                      pos_theirs, stage_log, _stream(stream)),
+           "fltee_stable_range_exchange_device")
+    return mine16
+
+
+def stable_range_merge(rec16, pos_base, stage_log, stream=None):
+    _check(L.lib().fltee_stable_range_merge_device(_ptr(rec16), _records16(rec16), pos_base,
+                                                   stage_log, _stream(stream)),
+           "fltee_stable_range_merge_device")
+    return rec16
+
+
+def stable_range_strip(rec16, out=None, stream=None):
+    """The range as the fold's 8-byte (idx, val) records (int64 [m])."""
+    m = _records16(rec16)
+    if out is None:
+        out = torch.empty(m, dtype=torch.int64, device=rec16.device)
+    _check(L.lib().fltee_stable_range_strip_device(_ptr(rec16), m, _ptr(out), _stream(stream)),
+           "fltee_stable_range_strip_device")
+    return out
+
+
 def nips19_build_range(records, nrec, r, d, tf, pos_base, m, out=None, stream=None):
     """Entries pos_base..pos_base+m-1 of nips19's padded array (records ++ Laplace dummies
     ++ pads, common.rs:164-197); r = laplace_r(...)[0], tf = int(T)."""

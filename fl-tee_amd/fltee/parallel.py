@@ -162,6 +162,19 @@ class DeviceRangeOps:
     def steps(self, x, pos, stage_log, step_top, step_bot):
         self.D.bitonic_range_steps(x, pos, stage_log, step_top, step_bot)
 
+    # alg 7's stable network: 16-byte records, int64 [C, 2] (fltee_stable_*_range_device)
+    def stable_sort(self, x, pos, valid=None):
+        self.D.stable_range_sort(x, pos, valid=valid)
+
+    def stable_merge(self, x, pos, stage_log):
+        self.D.stable_range_merge(x, pos, stage_log)
+
+    def stable_exchange(self, x, theirs, pos, pos_theirs, stage_log):
+        self.D.stable_range_exchange(x, theirs, pos, pos_theirs, stage_log)
+
+    def stable_strip(self, x):
+        return self.D.stable_range_strip(x)
+
     def fold(self, buf, origin, end, pos_base, fold_len, halo, key=0):
         """The range's fold into a buffer like `buf` (positions [origin, end) written) and
         its side records (fltee_fold_range_device)."""
@@ -467,9 +480,14 @@ def index_sharded_advanced(chunks, world, M, n_total, k, d, ops=None, comm=None,
     assert world & (world - 1) == 0 and M % world == 0
     ops = ops if ops is not None else DeviceRangeOps()
     comm = comm if comm is not None else VirtualRanks(world)
-    C = M // world
     chunks = distributed_network(chunks, world, M, ops, comm, exchange=exchange, spare=spare,
                                  valid=n_total * k + d)
+    return _sorted_ranges_tail(chunks, M // world, n_total, k, d, ops, comm, halo, root, dp)
+
+
+def _sorted_ranges_tail(chunks, C, n_total, k, d, ops, comm, halo, root, dp):
+    """What follows the sort, for `advanced` and alg 7 alike: the halo fold, the long-run
+    patch, the per-range compaction, the reduce to the root, the scale (and DP noise)."""
     fold_len = n_total * k + d
     # one fold with halo n (or the caller's), fixed cost: a run of more than halo + 1
     # entries (a client repeated an index) is finished by the patch, no rerun
@@ -495,3 +513,58 @@ def index_sharded_advanced(chunks, world, M, n_total, k, d, ops=None, comm=None,
     if dp is not None:
         ops.dp(out, dp["sigma"], dp["clipping"], n_total, dp.get("seed", 0))
     return out
+
+
+def distributed_stable_network(chunks, world, M, ops, comm, valid=None):
+    """alg 7's stable network (k_stable.hip: 16-byte records ascending by the u64 key idx <<
+    32 | position, directions from the global position) over M positions in `world` ranges
+    of C = M / world, in distributed_network's pairwise form: every range runs stages up to
+    C on its own, then each later stage swaps whole ranges with the partner r ^ (2^j / C)
+    for its steps j >= C and merges inside each range.  The same pad rule (valid): a range
+    of pads alone is not sorted, a stage skips the ranges at or past roundup(valid,
+    2^stage).  The chunks (int64 [C, 2]) are sorted in place."""
+    C = M // world
+    clog, mlog = C.bit_length() - 1, M.bit_length() - 1
+    assert 1 << clog == C and 1 << mlog == M
+    vbound = M if valid is None else min(int(valid), M)
+    if hasattr(comm, "ensure_init"):
+        comm.ensure_init()
+
+    def live_from(stage):
+        blk = 1 << stage
+        return min((vbound + blk - 1) // blk * blk, M)
+
+    for r, x in chunks.items():
+        lo = r * C
+        if lo < vbound:
+            ops.stable_sort(x, lo, valid=None if vbound - lo >= C else vbound - lo)
+    for stage in range(clog + 1, mlog + 1):
+        sf = live_from(stage)
+        live = {r: x for r, x in chunks.items() if r * C < sf}
+        for j in range(stage - 1, clog - 1, -1):
+            bit = 1 << (j - clog)
+            theirs = comm.swap(live, lambda q: q ^ bit) if live else {}
+            for r, x in live.items():
+                ops.stable_exchange(x, theirs[r], r * C, (r ^ bit) * C, stage)
+            del theirs
+        for r, x in live.items():
+            ops.stable_merge(x, r * C, stage)
+    return chunks
+
+
+def index_sharded_bubble(chunks, world, M, n_total, k, d, ops=None, comm=None, halo=None, root=0):
+    """aggregation_alg 7 (bubble_sort_based.rs) over the padded array of M = next_pow2(n_total
+    * k + d) entries split into `world` ranges of C = M / world.  `chunks` maps a range index
+    r to its C 16-byte entries (int64 [C, 2], positions [r*C, (r+1)*C), built by
+    fltee_stable_init_range); one entry per process under DistRanks, all of them under
+    VirtualRanks.  The stable network runs distributed with pairwise exchanges only
+    (distributed_stable_network); each range is then stripped to the fold's 8-byte records
+    and takes index_sharded_advanced's tail step for step: halo fold, long-run patch,
+    per-range compaction, one reduce, x 1f32/n.  Returns the averaged f32[d] on the root
+    (None elsewhere): the in-order client sum, bit-identical to one GPU's alg 7."""
+    assert world & (world - 1) == 0 and M % world == 0
+    ops = ops if ops is not None else DeviceRangeOps()
+    comm = comm if comm is not None else VirtualRanks(world)
+    chunks = distributed_stable_network(chunks, world, M, ops, comm, valid=n_total * k + d)
+    stripped = {r: ops.stable_strip(x) for r, x in chunks.items()}
+    return _sorted_ranges_tail(stripped, M // world, n_total, k, d, ops, comm, halo, root, None)

@@ -78,7 +78,11 @@ typedef uint64_t fltee_eid_t;
  *   - size limit: next_pow2(n * k + d) <= 2^29 records (the network holds 16 B per record,
  *     addressed with 64-bit byte offsets; positions are 32-bit), else INVALID_PARAMETER
  *     before any scratch is reserved;
- *   - FLTEE_OPT_CLIP / _DP / _ACCUMULATE / _NO_AVERAGE and n_avg as for advanced. */
+ *   - FLTEE_OPT_CLIP / _DP / _ACCUMULATE / _NO_AVERAGE and n_avg as for advanced;
+ *   - an eid over several GPUs (fltee_device_init_multi) shards the ECALL by position range,
+ *     like advanced: the stable network over W ranges of C = M / W 16-byte records (range
+ *     sorts, pairwise range exchanges, range merges: the fltee_stable_*_range pieces
+ *     below), then advanced's halo fold, compaction and reduce.  The same bits as one GPU. */
 #define FLTEE_ALG_BUBBLE 7u
 
 /* ------------------------------------------------------------------------ */
@@ -95,8 +99,11 @@ fltee_status_t fltee_device_fini(fltee_eid_t eid);
  * own PCIe link, RCCL gathers the averaged slices on the root (hip_devices[0]).
  * advanced: position-range sharded bitonic network (RCCL all-to-alls), halo fold,
  * compaction and one RCCL reduce.  nips19: the same network (pairwise exchanges), the
- * ranges' selected entries gathered in order to the root.  alg 6: the batches split
- * over the GPUs, the batch sums summed in order on the root.  Sparse flat algorithms
+ * ranges' selected entries gathered in order to the root.  alg 7 (once switched on,
+ * fltee_set_bubble_ecall): the stable network over position ranges of 16-byte records
+ * (pairwise range exchanges), then advanced's halo fold, compaction and reduce.  alg 6:
+ * the batches split over the GPUs, the batch sums summed in order on the root.  Sparse
+ * flat algorithms
  * run on the root.  Devices all distinct: RCCL over xGMI; the same device repeated n
  * times: n virtual ranks on that GPU (exchanges are device copies; for tests). */
 fltee_status_t fltee_device_init_multi(const int *hip_devices, int n, fltee_eid_t *eid);
@@ -364,6 +371,43 @@ fltee_status_t fltee_fold_range_patch_device(void *d_dst, size_t origin, size_t 
 fltee_status_t fltee_compact_range_device(const void *d_chunk, size_t c, size_t d, void *d_buf,
                                           void *d_tmp, float coef, float *d_out, void *stream);
 
+/* ---- position-range pieces of alg 7's stable network (multi-GPU) ----------
+ * The padded array of alg 7 (M = 2^j entries of 16 bytes {u64 key = idx << 32 | global
+ * position; f32 val; u32 pad}) split into W contiguous ranges of m = M/W records; range r
+ * holds global positions [r*m, (r+1)*m).  Run on every range, in this order, these pieces
+ * are fltee_stable_sort_device's network step for step:
+ *   init_range -> range_sort -> for each stage 2^s > m: (range_exchange with the partner
+ *   range for every step 2^j >= m, j = s-1 .. log2 m) then range_merge -> range_strip ->
+ *   the fold / compaction pieces of `advanced` above.
+ * Every piece refuses, by host arithmetic before any device call, with
+ * FLTEE_ERROR_INVALID_PARAMETER: m not a power of two, m < 2^12 (one LDS tile) or m > 2^29,
+ * a position that is not a multiple of m, or a range ending past 2^31. */
+/* entries pos_base .. pos_base+m-1 of records ++ (i, 0.0) for i < d ++ pads (key ~0,
+ * +0.0), each keyed with its global position; d_records holds the records at positions
+ * pos_base.. (read where position < nrec).  nrec + d < 2^31. */
+fltee_status_t fltee_stable_init_range_device(const void *d_records, size_t nrec, size_t d,
+                                              size_t pos_base, size_t m, void *d_dst16, void *stream);
+/* stages 1 .. log2 m of the network on one range; the direction of every compare-exchange
+ * comes from its GLOBAL position.  Entries valid .. m-1 of the range are identical pads
+ * (valid >= m: none): stage blocks made of pads alone are skipped, which leaves them as
+ * they are.  valid = 0: nothing to do. */
+fltee_status_t fltee_stable_range_sort_device(void *d_rec16, size_t m, size_t pos_base,
+                                              size_t valid, void *stream);      /* stages 1..log2 m */
+/* the step j = |pos_mine - pos_theirs| (>= m, a power of two: the two positions differ in
+ * that one bit) of stage 2^stage_log (> j) between this range and a copy of its partner's:
+ * d_mine[x] becomes the smaller or the larger of (d_mine[x], d_theirs[x]) by key — the
+ * smaller exactly when (this range is the lower one) == (bit stage_log of pos_mine is 0).
+ * Also refused: pos_mine == pos_theirs, a distance that is no power of two, stage_log not
+ * above log2 of the distance. */
+fltee_status_t fltee_stable_range_exchange_device(void *d_mine16, const void *d_theirs16, size_t m,
+                                                  size_t pos_mine, size_t pos_theirs,
+                                                  uint32_t stage_log, void *stream);
+/* the steps j = m/2 .. 1 of stage 2^stage_log (> m, else refused) on one range. */
+fltee_status_t fltee_stable_range_merge_device(void *d_rec16, size_t m, size_t pos_base,
+                                               uint32_t stage_log, void *stream); /* steps m/2..1 of a stage > m */
+/* m 16-byte records -> the fold's 8-byte (idx, val) records; a pad becomes (u32::MAX, +0.0). */
+fltee_status_t fltee_stable_range_strip_device(const void *d_rec16, size_t m, void *d_dst8, void *stream);
+
 /* nips19 by position range (the shuffle is the same kind of network): entries
  * pos_base .. pos_base+m-1 of records ++ d*tf Laplace dummies (common.rs:189-197;
  * d_r from fltee_laplace_r_device, tf = (usize)T) ++ (u32::MAX, 0.0) pads; and
@@ -402,8 +446,13 @@ void fltee_set_advanced_exact_runs(int on);
 /* ecall_secure_aggregation with aggregation_alg 7 (lib.rs:389, FLTEE_ALG_BUBBLE): off
  * (default) = refused with 0x2, as every earlier version of this library did; on = answered
  * with the enclave's in-order result (the staged and the pipelined path, DP, the round
- * counter; on an eid over several GPUs it runs on the root).  A host that sends alg 7
- * switches it on once at start-up.  The device API (fltee_aggregate_device) answers alg 7
+ * counter).  On an eid over several GPUs it is sharded by position range — the stable
+ * network over W ranges of C = M / W records, each GPU loading and decrypting the clients
+ * of its own range, then advanced's halo fold, compaction and reduce: the same bits —
+ * except for the shapes the group declines, which the root runs alone as before: C < 2^12,
+ * C < 16 W, a fold context (n rounded up to 16, plus 16) above C, M > 2^29, a request
+ * k other than the payload's, and everything under fltee_set_advanced_exact_runs(1).
+ * A host that sends alg 7 switches it on once at start-up.  The device API (fltee_aggregate_device) answers alg 7
  * whatever this says. */
 void fltee_set_bubble_ecall(int on);
 void fltee_debug_set_seed(uint64_t seed);
