@@ -404,5 +404,33 @@ hipError_t launch_aes_ctr_slice(const uint8_t *cipher, size_t n, size_t bytes_pe
                                 size_t rec_per_client, const uint32_t *round_keys, uint8_t *plain,
                                 uint64_t block_off, uint32_t idx_sub, hipStream_t s,
                                 uint32_t *zero_word = nullptr);
+// GCM's CTR half (fltee_set_upload_aead): keystream block i = E_K(IV || BE32(2 + i)); n
+// slices at in_stride -> rec_per_client records each at out_stride
+hipError_t launch_aes_ctr_gcm(const uint8_t *in, size_t n, size_t in_stride, size_t rec_per_client,
+                              const uint32_t *round_keys, uint8_t *out, size_t out_stride,
+                              const uint8_t iv[12], hipStream_t s, uint32_t *zero_word = nullptr);
+// per client H = E_K(0^128), E_K(IV || 0x00000001) from its round keys: sub[32 c ..]
+void aes128_gcm_subkeys(const uint32_t *rk, size_t n, const uint8_t iv[12], uint8_t *sub);
+void aes128_gcm_subkeys_portable(const uint32_t *rk, size_t n, const uint8_t iv[12], uint8_t *sub);
+void aes128_session_round_keys_portable(const uint32_t *ids, size_t n, uint32_t *rk);
+bool host_has_aesni();
+
+// k_ghash.hip: GHASH over n slices (ct_bytes of ciphertext at `stride`, the tag behind it).
+// sub: 32 bytes per client (above); aad: 64 bytes per client, zero padded; pow:
+// ghash_pow_bytes(n); part: ghash_part_bytes(n, ct_bytes, aad_len).  powers -> bulk ->
+// finish (emit: write the tag; else fail[c] = 0 / 1 and FLTEE_DEV_ERR_AUTH into *status).
+size_t ghash_segments(size_t ct_bytes, size_t aad_len);
+size_t ghash_pow_bytes(size_t n);
+size_t ghash_part_bytes(size_t n, size_t ct_bytes, size_t aad_len);
+hipError_t launch_ghash_powers(const uint8_t *sub, size_t n, void *pow, hipStream_t s);
+hipError_t launch_ghash_bulk(const uint8_t *cipher, size_t n, size_t stride, size_t ct_bytes,
+                             const uint8_t *aad, size_t aad_len, const void *pow, void *part,
+                             hipStream_t s);
+hipError_t launch_ghash_finish(uint8_t *cipher, size_t n, size_t stride, size_t ct_bytes,
+                               size_t aad_len, const uint8_t *sub, const void *pow, const void *part,
+                               bool emit, uint32_t *fail, uint32_t *status, hipStream_t s);
+void gf128_mul_host(const uint8_t a[16], const uint8_t b[16], uint8_t out[16]);
+void gcm_tag_host(const uint8_t h[16], const uint8_t ej0[16], const uint8_t *aad, size_t aad_len,
+                  const uint8_t *ct, size_t ct_len, uint8_t tag[16]);
 
 }  // namespace fltee

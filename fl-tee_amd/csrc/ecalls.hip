@@ -123,17 +123,126 @@ static void client_round_keys(const uint32_t *ids, size_t n, std::vector<uint32_
 // the decryption left after it (the part not hidden under the copies).
 constexpr size_t kLoadChunkBytes = (size_t)64 << 20;
 
+// ---- authenticated uploads (fltee_set_upload_aead; k_ghash.hip) ----------------------
+static bool g_upload_aead = false;
+
+// One call's GCM parameters: the IV, and aad_len bytes of AAD per client.
+struct GcmArgs {
+    uint8_t iv[12] = {};
+    std::vector<uint8_t> aad;
+    size_t aad_len = 0;
+};
+
+static inline void put_be32(uint8_t *p, uint32_t v) {
+    p[0] = (uint8_t)(v >> 24);
+    p[1] = (uint8_t)(v >> 16);
+    p[2] = (uint8_t)(v >> 8);
+    p[3] = (uint8_t)v;
+}
+
+// What the ECALLs bind: IV = BE32(fl_id) || BE32(round) || BE32(0), AAD = BE32(fl_id) ||
+// BE32(round) || BE32(client_id) || BE32(aggregation_alg)
+static void ecall_gcm_args(uint32_t fl_id, uint32_t round, const uint32_t *ids, size_t n,
+                           uint32_t alg, GcmArgs &g) {
+    put_be32(g.iv, fl_id);
+    put_be32(g.iv + 4, round);
+    put_be32(g.iv + 8, 0);
+    g.aad_len = 16;
+    g.aad.resize(n * 16);
+    for (size_t c = 0; c < n; ++c) {
+        put_be32(&g.aad[16 * c], fl_id);
+        put_be32(&g.aad[16 * c + 4], round);
+        put_be32(&g.aad[16 * c + 8], ids[c]);
+        put_be32(&g.aad[16 * c + 12], alg);
+    }
+}
+
+static bool gcm_sizes_ok(size_t ct_bytes, size_t aad_len) {
+    return aad_len <= FLTEE_GCM_MAX_AAD && (uint64_t)ct_bytes <= ((uint64_t)1 << 36) - 32;
+}
+
+// The device side of a call's keys: the round keys into c->round_keys, per client H and
+// E_K(J0) then the AAD padded to 64 bytes into c->gcm_sub (host: the caller's vector, alive
+// until the stream is synchronised), the powers of H into c->gcm_pow; the partial and fail
+// scratch reserved.  The word after the n fail words gathers FLTEE_DEV_ERR_AUTH for the
+// ECALLs.
+struct GcmDev {
+    const uint32_t *rk;
+    const uint8_t *sub, *aad;
+    const uint8_t *pow;
+    uint8_t *part;
+    uint32_t *fail, *auth_word;
+    size_t P;
+};
+
+static uint32_t gcm_prepare(DeviceCtx *c, const uint32_t *ids, size_t n, size_t ct_bytes,
+                            const uint8_t iv[12], const uint8_t *aad, size_t aad_len,
+                            std::vector<uint8_t> &host, hipStream_t s, GcmDev &d) {
+    const size_t rkb = n * 44 * 4, subb = n * 32, aadb = n * 64;
+    if (!c->round_keys.reserve(rkb) || !c->gcm_sub.reserve(subb + aadb) ||
+        !c->gcm_pow.reserve(ghash_pow_bytes(n)) ||
+        !c->gcm_part.reserve(ghash_part_bytes(n, ct_bytes, aad_len) + 16) ||
+        !c->gcm_fail.reserve(n * 4 + 16))
+        return FLTEE_ERROR_OUT_OF_MEMORY;
+    host.assign(rkb + subb + aadb, 0);
+    uint32_t *rk = (uint32_t *)host.data();
+    aes128_session_round_keys(ids, n, rk);
+    aes128_gcm_subkeys(rk, n, iv, host.data() + rkb);
+    for (size_t i = 0; i < n && aad_len; ++i)
+        std::memcpy(host.data() + rkb + subb + 64 * i, aad + aad_len * i, aad_len);
+    if (fl_memcpy_async(c->round_keys.ptr, host.data(), rkb, hipMemcpyHostToDevice, s) != hipSuccess ||
+        fl_memcpy_async(c->gcm_sub.ptr, host.data() + rkb, subb + aadb, hipMemcpyHostToDevice, s) != hipSuccess)
+        return FLTEE_ERROR_UNEXPECTED;
+    d.rk = (const uint32_t *)c->round_keys.ptr;
+    d.sub = (const uint8_t *)c->gcm_sub.ptr;
+    d.aad = d.sub + subb;
+    d.pow = (const uint8_t *)c->gcm_pow.ptr;
+    d.part = (uint8_t *)c->gcm_part.ptr;
+    d.fail = (uint32_t *)c->gcm_fail.ptr;
+    d.auth_word = d.fail + n;
+    d.P = ghash_segments(ct_bytes, aad_len);
+    if (launch_ghash_powers(d.sub, n, c->gcm_pow.ptr, s) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+    return FLTEE_SUCCESS;
+}
+
+// GHASH + tag check of the clients [c0, c0 + nc) of a prepared call: cipher points at client
+// c0's slice; fail[c0 ..] and *status are written
+static uint32_t gcm_verify(const GcmDev &d, size_t c0, size_t nc, const uint8_t *cipher, size_t ct_bytes,
+                           size_t aad_len, uint32_t *fail, uint32_t *status, hipStream_t s) {
+    const size_t stride = ct_bytes + FLTEE_GCM_TAG_BYTES;
+    const uint8_t *pow = d.pow + ghash_pow_bytes(c0);
+    uint8_t *part = d.part + c0 * d.P * 16;
+    if (launch_ghash_bulk(cipher, nc, stride, ct_bytes, d.aad + 64 * c0, aad_len, pow, part, s) != hipSuccess ||
+        launch_ghash_finish(const_cast<uint8_t *>(cipher), nc, stride, ct_bytes, aad_len, d.sub + 32 * c0,
+                            pow, part, false, fail + c0, status, s) != hipSuccess)
+        return FLTEE_ERROR_UNEXPECTED;
+    return FLTEE_SUCCESS;
+}
+
+// g (fltee_set_upload_aead): bpc is the slice stride B + 16; every chunk is authenticated
+// next to its decryption, and the word gathering FLTEE_DEV_ERR_AUTH is read at the
+// synchronisation that ends the decryption: FLTEE_ERROR_MAC_MISMATCH.
 static uint32_t load_and_decrypt(DeviceCtx *c, const uint32_t *ids, size_t n, const uint8_t *enc,
-                                 size_t bpc, float *t_load, float *t_dec) {
-    const size_t rpc = bpc / 8;
+                                 size_t bpc, float *t_load, float *t_dec, const GcmArgs *g = nullptr) {
+    const size_t ctb = g ? bpc - FLTEE_GCM_TAG_BYTES : bpc;
+    const size_t rpc = ctb / 8;
     const double t0 = now_s();
     if (!c->cipher.reserve(n * bpc) || !c->records.reserve(n * rpc * 8) ||
         !c->round_keys.reserve(n * 44 * 4))
         return FLTEE_ERROR_OUT_OF_MEMORY;
     std::vector<uint32_t> rk;
-    client_round_keys(ids, n, rk);
-    if (fl_memcpy_async(c->round_keys.ptr, rk.data(), rk.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return FLTEE_ERROR_UNEXPECTED;
+    std::vector<uint8_t> ghost;
+    GcmDev gd = {};
+    uint32_t auth = 0;
+    if (g) {
+        if (uint32_t st = gcm_prepare(c, ids, n, ctb, g->iv, g->aad.data(), g->aad_len, ghost, c->stream, gd))
+            return st;
+        if (fl_memset_async(gd.auth_word, 0, 4, c->stream) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+    } else {
+        client_round_keys(ids, n, rk);
+        if (fl_memcpy_async(c->round_keys.ptr, rk.data(), rk.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return FLTEE_ERROR_UNEXPECTED;
+    }
     size_t per = bpc ? kLoadChunkBytes / bpc : n;
     if (per == 0) per = 1;
     if ((n + per - 1) / per > (size_t)DeviceCtx::kCopyEvents) per = (n + DeviceCtx::kCopyEvents - 1) / DeviceCtx::kCopyEvents;
@@ -146,6 +255,14 @@ static uint32_t load_and_decrypt(DeviceCtx *c, const uint32_t *ids, size_t n, co
             hipEventRecord(c->copy_ev[ev], c->copy_stream) != hipSuccess ||
             hipStreamWaitEvent(c->stream, c->copy_ev[ev], 0) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
+        if (g) {
+            if (launch_aes_ctr_gcm(cipher + c0 * bpc, nc, bpc, rpc, gd.rk + c0 * 44,
+                                   (uint8_t *)c->records.ptr + c0 * rpc * 8, rpc * 8, g->iv,
+                                   c->stream) != hipSuccess ||
+                gcm_verify(gd, c0, nc, cipher + c0 * bpc, ctb, g->aad_len, gd.fail, gd.auth_word, c->stream))
+                return FLTEE_ERROR_UNEXPECTED;
+            continue;
+        }
         if (launch_aes_ctr(cipher + c0 * bpc, nc, bpc, rpc, (const uint32_t *)c->round_keys.ptr + c0 * 44,
                            (uint8_t *)c->records.ptr + c0 * rpc * 8, c->stream) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
@@ -153,10 +270,12 @@ static uint32_t load_and_decrypt(DeviceCtx *c, const uint32_t *ids, size_t n, co
     if (fl_stream_sync(c->copy_stream) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
     const double t1 = now_s();
     if (t_load) *t_load = (float)(t1 - t0);
+    if (g && fl_memcpy_async(&auth, gd.auth_word, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        return FLTEE_ERROR_UNEXPECTED;
     // rk lives on this stack frame: the decrypt (and the key upload) must finish here
     if (fl_stream_sync(c->stream) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
     if (t_dec) *t_dec = (float)(now_s() - t1);
-    return FLTEE_SUCCESS;
+    return auth ? FLTEE_ERROR_MAC_MISMATCH : FLTEE_SUCCESS;
 }
 
 static uint32_t read_status(DeviceCtx *c, uint32_t *st) {
@@ -509,8 +628,16 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     }
     // lib.rs:305-306: bytes per client floored, records per client floored; slice i
     // starts at i*bpc even when that is not a record boundary (ragged payloads)
+    // with authenticated uploads (fltee_set_upload_aead) a slice is B bytes || a 16-byte tag:
+    // bpc is the stride B + 16, the records are B's, and the payload is n whole slices
+    const bool aead = g_upload_aead;
     const size_t bpc = encrypted_parameters_size / n;
-    const size_t rpc = bpc / 8;
+    if (aead && (bpc < FLTEE_GCM_TAG_BYTES || encrypted_parameters_size % n ||
+                 !gcm_sizes_ok(bpc - FLTEE_GCM_TAG_BYTES, 16)))
+        return fail(FLTEE_ERROR_INVALID_PARAMETER);
+    const size_t rpc = (aead ? bpc - FLTEE_GCM_TAG_BYTES : bpc) / 8;
+    GcmArgs gcm;
+    if (aead) ecall_gcm_args(fl_id, round, client_ids, n, aggregation_alg, gcm);
     if ((aggregation_alg == FLTEE_ALG_ADVANCED || aggregation_alg == FLTEE_ALG_BUBBLE) &&
         n * num_of_sparse_parameters > n * rpc)
         return fail(FLTEE_ERROR_INVALID_PARAMETER);  // advanced.rs:72 out-of-bounds panic
@@ -519,7 +646,8 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     float *d_out = (float *)c->outbuf.ptr;
     const size_t k_req = num_of_sparse_parameters;
     const float coef = 1.0f / (float)n;
-    Group *G = group_of(eid);
+    // an authenticated upload on a multi-GPU eid: the root alone (GHASH is not sharded)
+    Group *G = aead ? nullptr : group_of(eid);
     uint32_t st = FLTEE_GROUP_FALLBACK;
     double t2 = 0;
     const bool flat = aggregation_alg == FLTEE_ALG_BASELINE || aggregation_alg == FLTEE_ALG_PATH_ORAM ||
@@ -569,8 +697,9 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         // "Aggregation" = the call minus its load and decrypt phases
         t2 = ta + execution_time_results[0] + execution_time_results[1];
     }
-    if (st == FLTEE_GROUP_FALLBACK && !G && n * bpc <= kStagedBytes) {
-        // one GPU, a small payload: one DMA each way, one host synchronisation
+    if (st == FLTEE_GROUP_FALLBACK && !G && !aead && n * bpc <= kStagedBytes) {
+        // one GPU, a small payload: one DMA each way, one host synchronisation (an
+        // authenticated upload needs the fail word before the aggregation: the path below)
         st = staged_ecall(c, aggregation_alg, client_ids, n, encrypted_parameters_data, bpc, d, k_req,
                           0, seed, cfg, updated_parameters_data, execution_time_results);
         if (st) {
@@ -587,8 +716,9 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     }
     if (st == FLTEE_GROUP_FALLBACK) {  // (a shape the per-GPU path declines comes here too)
         st = load_and_decrypt(c, client_ids, n, encrypted_parameters_data, bpc,
-                              &execution_time_results[0], &execution_time_results[1]);
-        if (st) return fail(st);
+                              &execution_time_results[0], &execution_time_results[1],
+                              aead ? &gcm : nullptr);
+        if (st) return fail(st);  // (a tag mismatch: the timers stay written)
         t2 = now_s();
         st = FLTEE_GROUP_FALLBACK;
         GroupInput in;
@@ -651,6 +781,11 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
     for (size_t i = 0; i < n; ++i)
         if (!g_keys.count(client_ids[i])) return fail(FLTEE_ERROR_UNEXPECTED);
 
+    const bool aead = g_upload_aead;
+    if (aead && !gcm_sizes_ok(k * 8, 16)) return fail(FLTEE_ERROR_INVALID_PARAMETER);
+    const size_t bpc6 = k * 8 + (aead ? FLTEE_GCM_TAG_BYTES : 0);  // the slice stride
+    GcmArgs gcm;
+    if (aead) ecall_gcm_args(fl_id, round, client_ids, n, aggregation_alg, gcm);
     float t_load = 0, t_dec = 0;
     const double t1 = now_s();
     const size_t halo6 = exact_runs_default() ? n * k + d : n;  // as aggregate_records
@@ -658,7 +793,7 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
     if (!c->outbuf.reserve(d * 4 + 16)) return fail(FLTEE_ERROR_OUT_OF_MEMORY);
     d_out = (float *)c->outbuf.ptr;
     uint32_t st;
-    Group *G = group_of(eid);
+    Group *G = aead ? nullptr : group_of(eid);  // authenticated: the root alone
     if (G && group_splits_host_copy(G)) {
         // the batches split over the eid's GPUs, each loading its own clients (group.hip)
         std::vector<uint32_t> rk;
@@ -671,7 +806,7 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
         in.t_dec = &t_dec;
         st = group_optimized(G, in, n, k, d, optimal_num_of_clients, 1.0f / (float)n, d_out, halo6);
         execution_time_results[0] = t_load;
-    } else if (!G && n * k * 8 <= kStagedBytes) {
+    } else if (!G && !aead && n * k * 8 <= kStagedBytes) {
         // one GPU, a small payload: one DMA each way, one host synchronisation
         st = staged_ecall(c, FLTEE_ALG_OPTIMIZED, client_ids, n, encrypted_parameters_data_ptr, k * 8, d,
                           k, optimal_num_of_clients, 0, cfg, updated_parameters_data, execution_time_results);
@@ -684,9 +819,11 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
         *retval = FLTEE_SUCCESS;
         return FLTEE_SUCCESS;
     } else {
-        st = load_and_decrypt(c, client_ids, n, encrypted_parameters_data_ptr, k * 8, &t_load, &t_dec);
-        if (st) return fail(st);
+        st = load_and_decrypt(c, client_ids, n, encrypted_parameters_data_ptr, bpc6, &t_load, &t_dec,
+                              aead ? &gcm : nullptr);
         execution_time_results[0] = t_load;
+        if (st == FLTEE_ERROR_MAC_MISMATCH) execution_time_results[1] = t_dec;
+        if (st) return fail(st);
         if (G) {
             GroupInput in;
             in.root_rec = (const uint64_t *)c->records.ptr;
@@ -737,6 +874,94 @@ extern "C" fltee_status_t fltee_decrypt_device(const uint32_t *client_ids, size_
                                                void *d_records, void *stream) {
     return aes_ctr_device(client_ids, n, d_cipher, bytes_per_client, d_records, (hipStream_t)stream);
 }
+
+// AES-128-GCM over n client slices (include/fltee_agg.h).  encrypt: plaintext slices of
+// ct_bytes in, (ciphertext || tag) slices out; else the reverse, with the tags verified.
+static fltee_status_t gcm_device(const uint32_t *client_ids, size_t n, const void *d_in, size_t ct_bytes,
+                                 const uint8_t *iv, const uint8_t *aad, size_t aad_len, void *d_out,
+                                 uint32_t *d_fail, bool encrypt, hipStream_t s) {
+    if (!gcm_sizes_ok(ct_bytes, aad_len) || !iv || (aad_len && !aad) || (encrypt && ct_bytes % 8))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    if (n == 0) return FLTEE_SUCCESS;
+    if (!client_ids || (!d_in && (ct_bytes || !encrypt)) || (!d_out && (encrypt || ct_bytes >= 8)) ||
+        (!encrypt && !d_fail))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    DeviceCtx *c = current_ctx();
+    if (!c) return FLTEE_ERROR_INVALID_PARAMETER;
+    std::vector<uint8_t> host;
+    GcmDev gd = {};
+    if (uint32_t st = gcm_prepare(c, client_ids, n, ct_bytes, iv, aad, aad_len, host, s, gd)) return st;
+    const size_t stride = ct_bytes + FLTEE_GCM_TAG_BYTES, rpc = ct_bytes / 8;
+    if (encrypt) {
+        uint8_t *ct = (uint8_t *)d_out;
+        if (launch_aes_ctr_gcm((const uint8_t *)d_in, n, ct_bytes, rpc, gd.rk, ct, stride, iv, s) != hipSuccess ||
+            launch_ghash_bulk(ct, n, stride, ct_bytes, gd.aad, aad_len, gd.pow, gd.part, s) != hipSuccess ||
+            launch_ghash_finish(ct, n, stride, ct_bytes, aad_len, gd.sub, gd.pow, gd.part, true, nullptr,
+                                nullptr, s) != hipSuccess)
+            return FLTEE_ERROR_UNEXPECTED;
+    } else {
+        const uint8_t *ct = (const uint8_t *)d_in;
+        if (gcm_verify(gd, 0, n, ct, ct_bytes, aad_len, d_fail, c->status, s) ||
+            launch_aes_ctr_gcm(ct, n, stride, rpc, gd.rk, (uint8_t *)d_out, rpc * 8, iv, s) != hipSuccess)
+            return FLTEE_ERROR_UNEXPECTED;
+    }
+    // the staged keys live on this stack frame: wait for the copies + kernels
+    return fl_stream_sync(s) == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_decrypt_auth_device(const uint32_t *client_ids, size_t n,
+                                                    const void *d_cipher, size_t ct_bytes,
+                                                    const uint8_t iv[12], const uint8_t *aad,
+                                                    size_t aad_len, void *d_records, uint32_t *d_fail,
+                                                    void *stream) {
+    return gcm_device(client_ids, n, d_cipher, ct_bytes, iv, aad, aad_len, d_records, d_fail, false,
+                      (hipStream_t)stream);
+}
+
+extern "C" fltee_status_t fltee_encrypt_auth_device(const uint32_t *client_ids, size_t n,
+                                                    const void *d_plain, size_t ct_bytes,
+                                                    const uint8_t iv[12], const uint8_t *aad,
+                                                    size_t aad_len, void *d_cipher, void *stream) {
+    return gcm_device(client_ids, n, d_plain, ct_bytes, iv, aad, aad_len, d_cipher, nullptr, true,
+                      (hipStream_t)stream);
+}
+
+extern "C" fltee_status_t fltee_debug_gcm_tag_host(uint32_t client_id, const uint8_t iv[12],
+                                                   const uint8_t *aad, size_t aad_len,
+                                                   const uint8_t *ct, size_t ct_len, uint8_t tag[16]) {
+    if (!gcm_sizes_ok(ct_len, aad_len) || !iv || !tag || (aad_len && !aad) || (ct_len && !ct))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    uint32_t rk[44];
+    uint8_t sub[32];
+    aes128_session_round_keys(&client_id, 1, rk);
+    aes128_gcm_subkeys(rk, 1, iv, sub);
+    gcm_tag_host(sub, sub + 16, aad, aad_len, ct, ct_len, tag);
+    return FLTEE_SUCCESS;
+}
+
+extern "C" void fltee_set_upload_aead(int on) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    g_upload_aead = on != 0;
+}
+
+// CPU self-test hooks: the one GF(2^128) multiply (GCM byte order), the subkeys H ||
+// E_K(J0) by the AES-NI or the portable path, the bulk kernel's segment size
+extern "C" void fltee_debug_gf128_mul(const uint8_t a[16], const uint8_t b[16], uint8_t out[16]) {
+    fltee::gf128_mul_host(a, b, out);
+}
+extern "C" int fltee_debug_gcm_subkeys(uint32_t client_id, const uint8_t iv[12], uint8_t sub[32],
+                                       int portable) {
+    uint32_t rk[44];
+    fltee::aes128_session_round_keys_portable(&client_id, 1, rk);
+    if (portable || !fltee::host_has_aesni()) {
+        fltee::aes128_gcm_subkeys_portable(rk, 1, iv, sub);
+        return 0;
+    }
+    fltee::aes128_gcm_subkeys(rk, 1, iv, sub);
+    return 1;
+}
+extern "C" size_t fltee_debug_gcm_segment_blocks(void) { return FLTEE_GCM_SEGMENT_BLOCKS; }
 
 // ------------------------------------------- client-side producers (§8f.4) ----
 extern "C" fltee_status_t fltee_encrypt_device(const uint32_t *client_ids, size_t n,

@@ -95,6 +95,8 @@ struct DeviceCtx {
     Buffer stage;                                        // small ECALLs: out, status, keys, ciphertext
     HostBuffer pin_in, pin_out;                          // small ECALLs: pinned staging both ways
     hipEvent_t call_ev[3] = {};                          // small ECALLs: the phase timers
+    // authenticated uploads (k_ghash.hip): subkeys + AAD, powers of H, partials, fail words
+    Buffer gcm_sub, gcm_pow, gcm_part, gcm_fail;
     Buffer ws_client, ws_client_coef;                   // client-side producers
     Buffer ws_cnt, ws_sel;                               // nips19's selected list
     Buffer ws_keys, ws_radix;  // ordered folds: records sorted by idx, the counting sort's scratch

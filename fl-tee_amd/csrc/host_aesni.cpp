@@ -59,4 +59,30 @@ void aes128_session_round_keys_aesni(const uint32_t *ids, size_t n, uint32_t *rk
     }
 }
 
+// GCM's per-client subkeys from the round keys above (rk: 44 words per client): H = E_K(0^128)
+// and E_K(J0), J0 = IV || 0x00000001, into sub[32 c ..] — two block encryptions per client
+__attribute__((target("aes,sse4.1"))) void aes128_gcm_subkeys_aesni(const uint32_t *rk, size_t n,
+                                                                    const uint8_t iv[12], uint8_t *sub) {
+    const __m128i bswap = _mm_setr_epi8(3, 2, 1, 0, 7, 6, 5, 4, 11, 10, 9, 8, 15, 14, 13, 12);
+    uint8_t j0b[16];
+    for (int i = 0; i < 12; ++i) j0b[i] = iv[i];
+    j0b[12] = j0b[13] = j0b[14] = 0;
+    j0b[15] = 1;
+    const __m128i j0 = _mm_loadu_si128(reinterpret_cast<const __m128i *>(j0b));
+    for (size_t c = 0; c < n; ++c) {
+        __m128i k[11];
+        for (int R = 0; R < 11; ++R)
+            k[R] = _mm_shuffle_epi8(_mm_loadu_si128(reinterpret_cast<const __m128i *>(rk + 44 * c + 4 * R)), bswap);
+        __m128i a = k[0], b = _mm_xor_si128(j0, k[0]);
+        for (int R = 1; R < 10; ++R) {
+            a = _mm_aesenc_si128(a, k[R]);
+            b = _mm_aesenc_si128(b, k[R]);
+        }
+        a = _mm_aesenclast_si128(a, k[10]);
+        b = _mm_aesenclast_si128(b, k[10]);
+        _mm_storeu_si128(reinterpret_cast<__m128i *>(sub + 32 * c), a);
+        _mm_storeu_si128(reinterpret_cast<__m128i *>(sub + 32 * c + 16), b);
+    }
+}
+
 }  // namespace fltee

@@ -170,6 +170,36 @@ void aes128_session_round_keys(const uint32_t *ids, size_t n, uint32_t *rk) {
     aes128_session_round_keys_portable(ids, n, rk);
 }
 
+// GCM's per-client subkeys next to the round keys (rk: 44 words per client): H = E_K(0^128)
+// and E_K(J0), J0 = IV || 0x00000001, into sub[32 c ..].  Portable: the bitsliced circuit,
+// the two blocks as slices 0 and 1 of the planes.
+void aes128_gcm_subkeys_aesni(const uint32_t *rk, size_t n, const uint8_t iv[12], uint8_t *sub);
+
+void aes128_gcm_subkeys_portable(const uint32_t *rk, size_t n, const uint8_t iv[12], uint8_t *sub) {
+    uint8_t j0[16];
+    for (int i = 0; i < 12; ++i) j0[i] = iv[i];
+    j0[12] = j0[13] = j0[14] = 0;
+    j0[15] = 1;
+    for (size_t c = 0; c < n; ++c) {
+        uint32_t st[16][8];
+        for (int p = 0; p < 16; ++p)
+            for (int i = 0; i < 8; ++i) st[p][i] = ((j0[p] >> i) & 1u) << 1;
+        add_round_key_bs<false>(st, rk + 44 * c);
+        aes128_rounds_bs(st, rk + 44 * c);
+        for (int b = 0; b < 2; ++b)
+            for (int p = 0; p < 16; ++p) {
+                uint32_t v = 0;
+                for (int i = 0; i < 8; ++i) v |= ((st[p][i] >> b) & 1u) << i;
+                sub[32 * c + 16 * b + p] = (uint8_t)v;
+            }
+    }
+}
+
+void aes128_gcm_subkeys(const uint32_t *rk, size_t n, const uint8_t iv[12], uint8_t *sub) {
+    if (host_has_aesni()) return aes128_gcm_subkeys_aesni(rk, n, iv, sub);
+    aes128_gcm_subkeys_portable(rk, n, iv, sub);
+}
+
 // host-side single block, for the CPU self-test (no GPU needed): slice 0 of the planes
 void aes128_encrypt_block_host(const uint8_t key[16], const uint8_t in[16], uint8_t out[16]) {
     uint32_t rk[44];
@@ -282,13 +312,22 @@ __device__ __forceinline__ void mix_ark_col(uint32_t s[4][8], uint32_t w) {
         for (int i = 0; i < 8; ++i) s[r][i] = ns[r][i];
 }
 
-template <bool ALIGNED>
+// GCM (k_ghash.hip's scheme): the counter block is IV (96 bits) || BE32(counter) — columns
+// 0-2 are the IV's words as per-call constant planes, column 3 the low counter word — and
+// the plaintext slices lie at ostride (the ciphertext slices carry a tag behind them).
+// The plain instantiation (GCM = false) never reads iv or ostride.
+struct GcmIv {
+    uint32_t w[3];  // the IV's big-endian words
+};
+
+template <bool ALIGNED, bool GCM = false>
 __global__ __launch_bounds__(256) void aes_ctr_bs4_kernel(const uint8_t *__restrict__ cipher,
                                                           size_t n, size_t bpc, size_t rpc,
                                                           const uint32_t *__restrict__ rks,
                                                           uint8_t *__restrict__ plain,
                                                           uint64_t block_off, uint32_t idx_sub,
-                                                          uint64_t wpc, uint32_t *__restrict__ zero_word) {
+                                                          uint64_t wpc, uint32_t *__restrict__ zero_word,
+                                                          size_t ostride, GcmIv iv) {
     if (zero_word && blockIdx.x == 0 && threadIdx.x == 0) *zero_word = 0u;
     const uint32_t lane = threadIdx.x & 63, col = lane & 3, g = lane >> 2;
     const uint64_t bpcl = (rpc + 1) / 2;  // 16-byte blocks per client
@@ -320,7 +359,12 @@ __global__ __launch_bounds__(256) void aes_ctr_bs4_kernel(const uint8_t *__restr
                                              : t == 6 ? 0xf0f0f0f0u : t == 7 ? 0xff00ff00u : 0xffff0000u)
                                           : 0u - ((wlo >> t) & 1u);
                 const uint32_t v2 = 0u - ((whi >> t) & 1u);
-                s[r][i] = col == 3 ? v3 : col == 2 ? v2 : 0u;
+                if (GCM) {
+                    const uint32_t ivc = col == 0 ? iv.w[0] : col == 1 ? iv.w[1] : iv.w[2];
+                    s[r][i] = col == 3 ? v3 : 0u - ((ivc >> t) & 1u);
+                } else {
+                    s[r][i] = col == 3 ? v3 : col == 2 ? v2 : 0u;
+                }
             }
         ark_col(s, rkw[0]);
 #pragma unroll 1
@@ -336,7 +380,7 @@ __global__ __launch_bounds__(256) void aes_ctr_bs4_kernel(const uint8_t *__restr
         // rows 8 r + i -> word j = keystream word `col` of block j
         transpose32(&s[0][0]);
         const uint8_t *cbase = cipher + c * bpc + 4 * col;
-        uint8_t *dbase = plain + c * rpc * 8 + 4 * col;
+        uint8_t *dbase = plain + c * (GCM ? ostride : rpc * 8) + 4 * col;
         const uint32_t sub = (col & 1) ? 0u : idx_sub;
 #pragma unroll
         for (int j = 0; j < 32; ++j) {
@@ -407,13 +451,14 @@ __device__ __forceinline__ void round_row(uint32_t x[8], uint32_t wr) {
     }
 }
 
-template <bool ALIGNED>
+template <bool ALIGNED, bool GCM = false>
 __global__ __launch_bounds__(256) void aes_ctr_row_kernel(const uint8_t *__restrict__ cipher,
                                                           size_t n, size_t bpc, size_t rpc,
                                                           const uint32_t *__restrict__ rks,
                                                           uint8_t *__restrict__ plain,
                                                           uint64_t block_off, uint32_t idx_sub,
-                                                          uint64_t wpc, uint32_t *__restrict__ zero_word) {
+                                                          uint64_t wpc, uint32_t *__restrict__ zero_word,
+                                                          size_t ostride, GcmIv iv) {
     if (zero_word && blockIdx.x == 0 && threadIdx.x == 0) *zero_word = 0u;
     __shared__ __attribute__((aligned(16))) uint8_t ks_lds[4][kAesWindowR * 16];
     uint8_t *ks = ks_lds[threadIdx.x >> 6];
@@ -459,7 +504,11 @@ __global__ __launch_bounds__(256) void aes_ctr_row_kernel(const uint8_t *__restr
             const int t = (int)((15 - 4 * p - r) * 8) + i;  // counter bit of this plane
             const uint32_t pat = t == 0 ? 0xaaaaaaaau : t == 1 ? 0xccccccccu : t == 2 ? 0xf0f0f0f0u
                                : t == 3 ? 0xff00ff00u : 0xffff0000u;
-            const uint32_t wb = t < 32 ? (wlo >> (t & 31)) & 1u : t < 64 ? (whi >> (t & 31)) & 1u : 0u;
+            // GCM: counter bits 32-127 are the IV's (the lane's column p < 3 is IV word p)
+            const uint32_t ivp = p == 0 ? iv.w[0] : p == 1 ? iv.w[1] : iv.w[2];
+            const uint32_t wb = t < 32 ? (wlo >> (t & 31)) & 1u
+                              : GCM    ? (ivp >> (t & 31)) & 1u
+                              : t < 64 ? (whi >> (t & 31)) & 1u : 0u;
             x[i] = t < 5 ? pat : t < 7 ? 0u - ((G >> (t - 5)) & 1u) : 0u - wb;
         }
 #pragma unroll
@@ -510,7 +559,7 @@ __global__ __launch_bounds__(256) void aes_ctr_row_kernel(const uint8_t *__restr
         __builtin_amdgcn_wave_barrier();  // the next window's stores after every read
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const uint32_t kw[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
-        uint8_t *dbase = plain + c * rpc * 8;
+        uint8_t *dbase = plain + c * (GCM ? ostride : rpc * 8);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const uint64_t ctr = W + 2 * lane + h;
@@ -527,10 +576,13 @@ __global__ __launch_bounds__(256) void aes_ctr_row_kernel(const uint8_t *__restr
 static int g_aes_variant = 0;  // 0: by size, 1: the quad kernel, 2: the byte-per-lane kernel
 void set_aes_variant(int v) { g_aes_variant = v; }
 
-hipError_t launch_aes_ctr_slice(const uint8_t *cipher, size_t n, size_t bytes_per_client,
-                                size_t rec_per_client, const uint32_t *round_keys, uint8_t *plain,
-                                uint64_t block_off, uint32_t idx_sub, hipStream_t s,
-                                uint32_t *zero_word) {
+// One launch of the CTR kernels.  GCM = false is the library's plain CTR, launch for launch
+// as before the IV existed (the kernels' iv and ostride arguments are never read).
+template <bool GCM>
+static hipError_t launch_ctr(const uint8_t *cipher, size_t n, size_t bytes_per_client,
+                             size_t rec_per_client, const uint32_t *round_keys, uint8_t *plain,
+                             uint64_t block_off, uint32_t idx_sub, hipStream_t s,
+                             uint32_t *zero_word, size_t ostride, GcmIv iv) {
     const size_t bpcl = (rec_per_client + 1) / 2;
     if (n == 0 || bpcl == 0)  // nothing to decrypt; the word still has to read 0
         return zero_word ? fl_memset_async(zero_word, 0, 4, s) : hipSuccess;
@@ -544,27 +596,66 @@ hipError_t launch_aes_ctr_slice(const uint8_t *cipher, size_t n, size_t bytes_pe
         const uint64_t wpcr = (block_off + bpcl - 1) / kAesWindowR - block_off / kAesWindowR + 1;
         uint64_t rblocks = ((uint64_t)n * wpcr + 3) / 4;
         if (rblocks > 16384) rblocks = 16384;
-        if (aligned)
+        if (GCM) {
+            if (aligned)
+                FLTEE_LAUNCH((aes_ctr_row_kernel<true, true>), dim3((unsigned)rblocks), dim3(256), 0, s,
+                                   cipher, n, bytes_per_client, rec_per_client, round_keys, plain,
+                                   block_off, idx_sub, wpcr, zero_word, ostride, iv);
+            else
+                FLTEE_LAUNCH((aes_ctr_row_kernel<false, true>), dim3((unsigned)rblocks), dim3(256), 0, s,
+                                   cipher, n, bytes_per_client, rec_per_client, round_keys, plain,
+                                   block_off, idx_sub, wpcr, zero_word, ostride, iv);
+        } else if (aligned)
             FLTEE_LAUNCH(aes_ctr_row_kernel<true>, dim3((unsigned)rblocks), dim3(256), 0, s,
                                cipher, n, bytes_per_client, rec_per_client, round_keys, plain,
-                               block_off, idx_sub, wpcr, zero_word);
+                               block_off, idx_sub, wpcr, zero_word, ostride, iv);
         else
             FLTEE_LAUNCH(aes_ctr_row_kernel<false>, dim3((unsigned)rblocks), dim3(256), 0, s,
                                cipher, n, bytes_per_client, rec_per_client, round_keys, plain,
-                               block_off, idx_sub, wpcr, zero_word);
+                               block_off, idx_sub, wpcr, zero_word, ostride, iv);
         return hipGetLastError();
     }
     uint64_t blocks = (waves + 3) / 4;
     if (blocks > 16384) blocks = 16384;  // grid-stride beyond 16 waves per SIMD
-    if (aligned)
+    if (GCM) {
+        if (aligned)
+            FLTEE_LAUNCH((aes_ctr_bs4_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, s,
+                               cipher, n, bytes_per_client, rec_per_client, round_keys, plain,
+                               block_off, idx_sub, wpc, zero_word, ostride, iv);
+        else
+            FLTEE_LAUNCH((aes_ctr_bs4_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, s,
+                               cipher, n, bytes_per_client, rec_per_client, round_keys, plain,
+                               block_off, idx_sub, wpc, zero_word, ostride, iv);
+    } else if (aligned)
         FLTEE_LAUNCH(aes_ctr_bs4_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s,
                            cipher, n, bytes_per_client, rec_per_client, round_keys, plain,
-                           block_off, idx_sub, wpc, zero_word);
+                           block_off, idx_sub, wpc, zero_word, ostride, iv);
     else
         FLTEE_LAUNCH(aes_ctr_bs4_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s,
                            cipher, n, bytes_per_client, rec_per_client, round_keys, plain,
-                           block_off, idx_sub, wpc, zero_word);
+                           block_off, idx_sub, wpc, zero_word, ostride, iv);
     return hipGetLastError();
+}
+
+hipError_t launch_aes_ctr_slice(const uint8_t *cipher, size_t n, size_t bytes_per_client,
+                                size_t rec_per_client, const uint32_t *round_keys, uint8_t *plain,
+                                uint64_t block_off, uint32_t idx_sub, hipStream_t s,
+                                uint32_t *zero_word) {
+    return launch_ctr<false>(cipher, n, bytes_per_client, rec_per_client, round_keys, plain,
+                             block_off, idx_sub, s, zero_word, 0, GcmIv{{0u, 0u, 0u}});
+}
+
+// GCM's CTR half: keystream block i = E_K(IV || BE32(2 + i)); n slices at in_stride ->
+// rec_per_client records each at out_stride (either side may carry a tag behind its slice)
+hipError_t launch_aes_ctr_gcm(const uint8_t *in, size_t n, size_t in_stride, size_t rec_per_client,
+                              const uint32_t *round_keys, uint8_t *out, size_t out_stride,
+                              const uint8_t iv[12], hipStream_t s, uint32_t *zero_word) {
+    GcmIv w;
+    for (int j = 0; j < 3; ++j)
+        w.w[j] = ((uint32_t)iv[4 * j] << 24) | ((uint32_t)iv[4 * j + 1] << 16) |
+                 ((uint32_t)iv[4 * j + 2] << 8) | iv[4 * j + 3];
+    return launch_ctr<true>(in, n, in_stride, rec_per_client, round_keys, out, 2, 0, s, zero_word,
+                            out_stride, w);
 }
 
 hipError_t launch_aes_ctr(const uint8_t *cipher, size_t n, size_t bytes_per_client,

@@ -17,6 +17,7 @@ ERROR_UNEXPECTED = 0x1
 ERROR_INVALID_PARAMETER = 0x2
 ERROR_OUT_OF_MEMORY = 0x3
 ERROR_INVALID_ENCLAVE_ID = 0x2002
+ERROR_MAC_MISMATCH = 0x3001  # an authenticated upload's GCM tag did not verify
 
 ALG_ADVANCED, ALG_NIPS19, ALG_BASELINE, ALG_NON_OBLIVIOUS, ALG_PATH_ORAM, ALG_OPTIMIZED = 1, 2, 3, 4, 5, 6
 ALG_BUBBLE = 7  # lib.rs:389 (the reference bench's `-a bubble`; not in option.py, not in ALG_CODES)
@@ -28,6 +29,12 @@ ALG_CODES = {  # src/option.py:131-145
 DEV_ERR_DENSE_ORDER = 0x1
 DEV_ERR_INDEX_RANGE = 0x2
 DEV_ERR_FOLD_OVERFLOW = 0x4  # retired in round 6: never set
+DEV_ERR_AUTH = 0x10
+
+# authenticated uploads (AES-128-GCM; k_ghash.hip)
+GCM_SEGMENT_BLOCKS = 512  # FLTEE_GCM_SEGMENT_BLOCKS: 16-byte blocks per GHASH segment
+GCM_TAG_BYTES = 16
+GCM_MAX_AAD = 64
 
 OPT_DENSE = 0x1
 OPT_DP = 0x2
@@ -69,6 +76,10 @@ SIGNATURES = {
     "fltee_workspace_bytes": (_S, [_U32, _S, _S, _S, ctypes.POINTER(DeviceOpts)]),
     "fltee_reserve": (_U32, [_U32, _S, _S, _S, ctypes.POINTER(DeviceOpts)]),
     "fltee_decrypt_device": (_U32, [_P, _S, _P, _S, _P, _P]),
+    "fltee_decrypt_auth_device": (_U32, [_P, _S, _P, _S, _P, _P, _S, _P, _P, _P]),
+    "fltee_encrypt_auth_device": (_U32, [_P, _S, _P, _S, _P, _P, _S, _P, _P]),
+    "fltee_debug_gcm_tag_host": (_U32, [_U32, _P, _P, _S, _P, _S, _P]),
+    "fltee_set_upload_aead": (None, [ctypes.c_int]),
     "fltee_device_status": (_U32, [_P, _P]),
     "fltee_sum_rows_device": (_U32, [_P, _S, _S, _F, _P, _P]),
     "fltee_dp_noise_device": (_U32, [_P, _S, _F, _F, _S, _U64, _P]),
@@ -111,6 +122,9 @@ SIGNATURES = {
 }
 EXTRA_SIGNATURES = {  # test hooks not in the public header
     "fltee_debug_aes_block": (None, [_P, _P, _P]),
+    "fltee_debug_gf128_mul": (None, [_P, _P, _P]),
+    "fltee_debug_gcm_subkeys": (ctypes.c_int, [_U32, _P, _P, ctypes.c_int]),
+    "fltee_debug_gcm_segment_blocks": (_S, []),
     "fltee_debug_set_dense_variant": (None, [ctypes.c_int]),
     "fltee_debug_set_oram_bucket": (None, [ctypes.c_int]),
     "fltee_debug_set_aes_variant": (None, [ctypes.c_int]),

@@ -19,6 +19,7 @@ The payload can go into an Aggregate request as is, or straight to the device-si
 aggregation (fltee_decrypt_device + fltee_aggregate_device) for a GPU-resident round.
 """
 import ctypes
+import struct
 
 import numpy as np
 import torch
@@ -72,6 +73,44 @@ def encrypt_parameters(records, client_ids, stream=None):
                                         plain.numel() // n, _ptr(out), _stream(stream)),
            "fltee_encrypt_device")
     return out
+
+
+def ecall_iv(fl_id, round_):
+    """The 12-byte IV the ECALLs use with authenticated uploads: BE32(fl_id) || BE32(round) ||
+    BE32(0)."""
+    return struct.pack(">III", fl_id, round_, 0)
+
+
+def ecall_aad(fl_id, round_, client_ids, aggregation_alg):
+    """The ECALLs' AAD, 16 bytes per client: BE32(fl_id) || BE32(round) || BE32(client_id) ||
+    BE32(aggregation_alg) — a slice cannot be replayed in another round, moved to another
+    client or submitted under another algorithm."""
+    return b"".join(struct.pack(">IIII", fl_id, round_, int(c), aggregation_alg) for c in client_ids)
+
+
+def encrypt_parameters_gcm(records, client_ids, iv, aad=b"", stream=None):
+    """AES-128-GCM of n clients' records (equal counts) -> uint8 [n, B + 16]: ciphertext ||
+    tag per client, one 12-byte IV, aad = n equal parts of at most 64 bytes."""
+    ids = np.ascontiguousarray(client_ids, dtype=np.uint32)
+    n = len(ids)
+    plain = records.contiguous().view(torch.uint8).reshape(-1)
+    assert len(iv) == 12 and plain.numel() % n == 0 and len(aad) % n == 0
+    B = plain.numel() // n
+    out = torch.empty(n * (B + L.GCM_TAG_BYTES), dtype=torch.uint8, device=plain.device)
+    ivb = (ctypes.c_uint8 * 12)(*iv)
+    aadb = (ctypes.c_uint8 * max(len(aad), 1))(*aad)
+    _check(L.lib().fltee_encrypt_auth_device(ids.ctypes.data_as(ctypes.c_void_p), n, _ptr(plain), B,
+                                             ivb, aadb, len(aad) // n, _ptr(out), _stream(stream)),
+           "fltee_encrypt_auth_device")
+    return out.reshape(n, B + L.GCM_TAG_BYTES)
+
+
+def encrypt_parameters_auth(records, client_ids, fl_id, round_, aggregation_alg, stream=None):
+    """The authenticated upload of an ECALL (fltee.ecalls.set_upload_aead): the payload of
+    ecall_secure_aggregation(fl_id, round_, client_ids, ..., aggregation_alg)."""
+    return encrypt_parameters_gcm(records, client_ids, ecall_iv(fl_id, round_),
+                                  ecall_aad(fl_id, round_, client_ids, aggregation_alg),
+                                  stream).reshape(-1)
 
 
 def produce_payloads(values, client_ids, k=None, clipping=None, stream=None):

@@ -117,6 +117,25 @@ def decrypt(client_ids, cipher, bytes_per_client, records, stream=None):
     return records
 
 
+def decrypt_auth(client_ids, cipher, ct_bytes, iv, aad=b"", records=None, stream=None):
+    """AES-128-GCM decrypt of n slices of (ct_bytes || 16-byte tag): (records, fail) with
+    fail[c] = 1 where client c's tag did not verify (FLTEE_DEV_ERR_AUTH is then set in the
+    status word)."""
+    ids = np.ascontiguousarray(client_ids, dtype=np.uint32)
+    n = len(ids)
+    assert len(iv) == 12 and len(aad) % max(n, 1) == 0
+    if records is None:
+        records = torch.empty(max(n * (ct_bytes // 8), 1), dtype=torch.int64, device=cipher.device)
+    fail = torch.full((max(n, 1),), 0x7fffffff, dtype=torch.int32, device=cipher.device)
+    ivb = (ctypes.c_uint8 * 12)(*iv)
+    aadb = (ctypes.c_uint8 * max(len(aad), 1))(*aad)
+    _check(L.lib().fltee_decrypt_auth_device(ids.ctypes.data_as(ctypes.c_void_p), n, _ptr(cipher),
+                                             ct_bytes, ivb, aadb, len(aad) // max(n, 1),
+                                             _ptr(records), _ptr(fail), _stream(stream)),
+           "fltee_decrypt_auth_device")
+    return records[:n * (ct_bytes // 8)], fail[:n]
+
+
 def laplace_r(d, k, n, seed, device="cuda", stream=None):
     r = torch.empty(d, dtype=torch.int32, device=device)
     T = ctypes.c_float(0)

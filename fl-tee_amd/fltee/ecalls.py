@@ -92,7 +92,7 @@ class Enclave:
                                                        aggregation_alg):
         ids = np.ascontiguousarray(client_ids, dtype=np.uint32)
         enc = _as_u8(encrypted_parameters)
-        need = len(ids) * num_of_sparse_parameters * 8
+        need = len(ids) * (num_of_sparse_parameters * 8 + (L.GCM_TAG_BYTES if _upload_aead else 0))
         if enc.nbytes < need:  # [user_check]: the enclave would read past the buffer
             raise ValueError(f"payload has {enc.nbytes} bytes, alg 6 reads {need}")
         out = np.full(num_of_parameters, np.nan, dtype=np.float32)
@@ -114,6 +114,20 @@ def set_path_oram_tree(on):
     """aggregation_alg 5 through the ECALLs: the tree Path ORAM (oram.rs:64-118) when on, the
     output-equivalent oblivious sweep (default) when off (fltee_set_path_oram_tree)."""
     L.lib().fltee_set_path_oram_tree(1 if on else 0)
+
+
+_upload_aead = False
+
+
+def set_upload_aead(on):
+    """The ECALLs' upload format: plain AES-128-CTR when off (default, lib.rs:312-343);
+    AES-128-GCM when on — a client's slice is ciphertext || 16-byte tag under IV = BE32(fl_id)
+    || BE32(round) || BE32(0) and AAD = BE32(fl_id) || BE32(round) || BE32(client_id) ||
+    BE32(aggregation_alg) (fltee.client.encrypt_parameters_auth builds it); a slice that does
+    not verify ends the ECALL with retval 0x3001 (fltee_set_upload_aead)."""
+    global _upload_aead
+    L.lib().fltee_set_upload_aead(1 if on else 0)
+    _upload_aead = bool(on)
 
 
 def set_bubble_ecall(on):

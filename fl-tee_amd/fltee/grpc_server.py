@@ -114,10 +114,12 @@ def main(argv=None):
     ap.add_argument("--dp", action="store_true", help="DP noise on (server.rs:237 forces off)")
     ap.add_argument("--strict-reference", action="store_true",
                     help="apply server.rs:126-128's optimal_num_of_clients check to every alg")
+    ap.add_argument("--aead", action="store_true",
+                    help="authenticated uploads: AES-128-GCM, ciphertext || 16-byte tag per client")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     agg = Aggregator(device=args.device, verbose=not args.quiet, dp=args.dp,
-                     strict_reference=args.strict_reference)
+                     strict_reference=args.strict_reference, aead=args.aead)
     server, port = make_server(agg, args.address, verbose=not args.quiet)
     server.start()
     print(f"[Server] Now GRPC Server is binded on {args.address} (port {port})", flush=True)

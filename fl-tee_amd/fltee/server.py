@@ -11,11 +11,14 @@ request).  Documented deviations from the reference host:
     check is applied only when aggregation_alg == 6 (`strict_reference=True`
     restores the reference behaviour).
   * server.rs:237 hard-wires dp = false; here it is a constructor argument.
+  * `aead=True` (off by default) switches the uploads to AES-128-GCM: the request's
+    encrypted_parameters then carries ciphertext || 16-byte tag per client (the proto is
+    unchanged), and a slice that does not verify is a ServerPanic naming the MAC mismatch.
 """
 import time
 
 from . import _lib as L
-from .ecalls import Enclave
+from .ecalls import Enclave, set_upload_aead
 
 
 class ServerPanic(RuntimeError):
@@ -23,8 +26,12 @@ class ServerPanic(RuntimeError):
 
 
 class Aggregator:
-    def __init__(self, device=0, verbose=False, dp=False, strict_reference=False, enclave=None):
+    def __init__(self, device=0, verbose=False, dp=False, strict_reference=False, enclave=None,
+                 aead=False):
         self.enclave = enclave if enclave is not None else Enclave(device)
+        self.aead = bool(aead)
+        if self.aead:  # process-wide, like the enclave's other start-up switches
+            set_upload_aead(True)
         self.verbose = verbose
         self.dp = dp
         self.strict_reference = strict_reference
@@ -54,12 +61,16 @@ class Aggregator:
             st, rv, out, times = self.enclave.ecall_client_size_optimized_secure_aggregation(
                 fl_id, round, optimal_num_of_clients, client_ids, encrypted_parameters,
                 num_of_parameters, num_of_sparse_parameters, aggregation_alg)
+            if st == L.SUCCESS and rv == L.ERROR_MAC_MISMATCH:
+                raise ServerPanic("MAC mismatch at ecall_client_size_optimized_secure_aggregation")
             if st != L.SUCCESS or rv != L.SUCCESS:
                 raise ServerPanic("Error at ecall_client_size_optimized_secure_aggregation")
         else:
             st, rv, out, times = self.enclave.ecall_secure_aggregation(
                 fl_id, round, client_ids, encrypted_parameters, num_of_parameters,
                 num_of_sparse_parameters, aggregation_alg)
+            if st == L.SUCCESS and rv == L.ERROR_MAC_MISMATCH:
+                raise ServerPanic("MAC mismatch at ecall_secure_aggregation")
             if st != L.SUCCESS or rv != L.SUCCESS:
                 raise ServerPanic("Error at ecall_secure_aggregation")
         elapsed = time.perf_counter() - t0

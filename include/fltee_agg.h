@@ -51,6 +51,8 @@ typedef uint32_t fltee_status_t;
 #define FLTEE_ERROR_INVALID_PARAMETER 0x0002u
 #define FLTEE_ERROR_OUT_OF_MEMORY 0x0003u
 #define FLTEE_ERROR_INVALID_ENCLAVE_ID 0x2002u
+#define FLTEE_ERROR_MAC_MISMATCH 0x3001u /* sgx_error.h SGX_ERROR_MAC_MISMATCH: an upload's
+                                            GCM tag did not verify (fltee_set_upload_aead) */
 
 /* sgx_enclave_id_t */
 typedef uint64_t fltee_eid_t;
@@ -168,6 +170,7 @@ fltee_status_t ecall_client_size_optimized_secure_aggregation(
 #define FLTEE_DEV_ERR_FOLD_OVERFLOW 0x4u /* retired in round 6 (advanced's fold finishes runs
                                            of any length); never set */
 #define FLTEE_DEV_ERR_ORAM_STASH 0x8u    /* path_oram tree mode: the stash (20) overflowed */
+#define FLTEE_DEV_ERR_AUTH 0x10u          /* an authenticated slice's tag did not verify */
 #define FLTEE_DEV_ERR_LAUNCH 0x80000000u
 
 /* option flags */
@@ -261,6 +264,45 @@ fltee_status_t fltee_client_clip_device(void *d_records, size_t n, size_t k, flo
  * 2-byte key layout), bytes_per_client each; the inverse of fltee_decrypt_device. */
 fltee_status_t fltee_encrypt_device(const uint32_t *client_ids, size_t n, const void *d_plain,
                                     size_t bytes_per_client, void *d_cipher, void *stream);
+
+/* ---- authenticated uploads: AES-128-GCM (NIST SP 800-38D), 96-bit IV, 128-bit tag ------
+ * Per client: K = the session key, H = E_K(0^128), J0 = IV || 0x00000001, keystream block
+ * i = E_K(IV || BE32(2 + i)), T = GHASH_H(AAD || pad || C || pad || BE64(8 |AAD|) ||
+ * BE64(8 |C|)) ^ E_K(J0).  GHASH runs on the GPU in constant time (k_ghash.hip), in
+ * segments of FLTEE_GCM_SEGMENT_BLOCKS 16-byte blocks.  Refused by host arithmetic with
+ * FLTEE_ERROR_INVALID_PARAMETER: aad_len > 64, ct_bytes > 2^36 - 32 (the 32-bit counter
+ * would wrap), and for the producer a ct_bytes that is no multiple of 8 (whole records). */
+#define FLTEE_GCM_SEGMENT_BLOCKS 512
+#define FLTEE_GCM_TAG_BYTES 16
+#define FLTEE_GCM_MAX_AAD 64
+/* n slices of (ct_bytes || 16-byte tag) at stride ct_bytes+16; one 12-byte IV for the call;
+ * aad: n x aad_len bytes (aad_len <= 64, may be 0).  Writes n * floor(ct_bytes/8) records and
+ * d_fail[n] (u32 0/1); ORs FLTEE_DEV_ERR_AUTH into the status word on any mismatch.  The
+ * computed tags never leave the device. */
+fltee_status_t fltee_decrypt_auth_device(const uint32_t *client_ids, size_t n, const void *d_cipher,
+                                         size_t ct_bytes, const uint8_t iv[12], const uint8_t *aad,
+                                         size_t aad_len, void *d_records, uint32_t *d_fail,
+                                         void *stream);
+/* the inverse: the client producer (ciphertext || tag per client); n slices of ct_bytes of
+ * plaintext in, n slices of ct_bytes + 16 out */
+fltee_status_t fltee_encrypt_auth_device(const uint32_t *client_ids, size_t n, const void *d_plain,
+                                         size_t ct_bytes, const uint8_t iv[12], const uint8_t *aad,
+                                         size_t aad_len, void *d_cipher, void *stream);
+/* the same tag computed on the host by the same multiply (no GPU): for CPU tests */
+fltee_status_t fltee_debug_gcm_tag_host(uint32_t client_id, const uint8_t iv[12], const uint8_t *aad,
+                                        size_t aad_len, const uint8_t *ct, size_t ct_len,
+                                        uint8_t tag[16]);
+/* The ECALLs' upload format.  Off (default): plain AES-128-CTR with a zero counter block, as
+ * lib.rs:312-343 and every earlier version of this library.  On: client c's slice is
+ * ciphertext (B bytes) || tag (16 bytes) of the scheme above with
+ *     IV  = BE32(fl_id) || BE32(round) || BE32(0)
+ *     AAD = BE32(fl_id) || BE32(round) || BE32(client_id) || BE32(aggregation_alg),
+ * so encrypted_parameters_size = n (B + 16) (alg 6 reads client_size (k 8 + 16) bytes) and
+ * the records per client are floor(B / 8).  The existing refusals come first and stay 0x2;
+ * a slice whose tag does not verify ends the call with *retval = FLTEE_ERROR_MAC_MISMATCH
+ * before any aggregation is launched, [out] zero-filled, the round not advanced.  An eid over
+ * several GPUs runs an authenticated ECALL on its root alone (the same bits). */
+void fltee_set_upload_aead(int on);
 
 /* out[j] = coef * sum_r rows[r*d + j], rows added in order (exact fp32): the
  * root-side combine of per-GPU partial sums, in the batch order of alg 6
