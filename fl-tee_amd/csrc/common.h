@@ -409,6 +409,13 @@ hipError_t launch_aes_ctr_slice(const uint8_t *cipher, size_t n, size_t bytes_pe
 hipError_t launch_aes_ctr_gcm(const uint8_t *in, size_t n, size_t in_stride, size_t rec_per_client,
                               const uint32_t *round_keys, uint8_t *out, size_t out_stride,
                               const uint8_t iv[12], hipStream_t s, uint32_t *zero_word = nullptr);
+// the same on the blocks [first_block, first_block + ceil(rec_per_client / 2)) of every slice
+// (a column shard): keystream block i = E_K(IV || BE32(2 + first_block + i)), the offset in
+// the counter planes as launch_aes_ctr_slice's; idx_sub subtracted from each idx
+hipError_t launch_aes_ctr_gcm_slice(const uint8_t *in, size_t n, size_t in_stride, size_t rec_per_client,
+                                    const uint32_t *round_keys, uint8_t *out, size_t out_stride,
+                                    const uint8_t iv[12], uint64_t first_block, uint32_t idx_sub,
+                                    hipStream_t s);
 // per client H = E_K(0^128), E_K(IV || 0x00000001) from its round keys: sub[32 c ..]
 void aes128_gcm_subkeys(const uint32_t *rk, size_t n, const uint8_t iv[12], uint8_t *sub);
 void aes128_gcm_subkeys_portable(const uint32_t *rk, size_t n, const uint8_t iv[12], uint8_t *sub);
@@ -429,6 +436,24 @@ hipError_t launch_ghash_bulk(const uint8_t *cipher, size_t n, size_t stride, siz
 hipError_t launch_ghash_finish(uint8_t *cipher, size_t n, size_t stride, size_t ct_bytes,
                                size_t aad_len, const uint8_t *sub, const void *pow, const void *part,
                                bool emit, uint32_t *fail, uint32_t *status, hipStream_t s);
+// A window of every slice (a column shard): n rows at `stride` holding the ciphertext blocks
+// [first_block, first_block + ceil(win_bytes / 16)); part (n x P x 16 bytes, the whole slice's
+// segment layout) is zero but for the segments the window touches.  with_aad: this window also
+// takes the AAD blocks (exactly one window of a slice does).  merge: acc ^= part.  The XOR of a
+// slice's windows' parts is launch_ghash_bulk's part.  finish_tags: the finish with client c's
+// tag at tags + c * tag_stride, not behind the ciphertext.
+hipError_t launch_ghash_window(const uint8_t *window, size_t n, size_t stride, size_t ct_bytes,
+                               uint64_t first_block, size_t win_bytes, const uint8_t *aad,
+                               size_t aad_len, bool with_aad, const void *pow, void *part,
+                               hipStream_t s);
+hipError_t launch_ghash_merge(void *acc, const void *part, size_t n, size_t P, hipStream_t s);
+hipError_t launch_ghash_finish_tags(uint8_t *tags, size_t tag_stride, size_t n, size_t ct_bytes,
+                                    size_t aad_len, const uint8_t *sub, const void *pow,
+                                    const void *part, bool emit, uint32_t *fail, uint32_t *status,
+                                    hipStream_t s);
+void ghash_window_host(const uint8_t h[16], const uint8_t *aad, size_t aad_len, bool with_aad,
+                       const uint8_t *ct_window, size_t ct_bytes, uint64_t first_block,
+                       size_t win_bytes, uint8_t *part_out);
 void gf128_mul_host(const uint8_t a[16], const uint8_t b[16], uint8_t out[16]);
 void gcm_tag_host(const uint8_t h[16], const uint8_t ej0[16], const uint8_t *aad, size_t aad_len,
                   const uint8_t *ct, size_t ct_len, uint8_t tag[16]);

@@ -175,6 +175,18 @@ struct GcmDev {
     size_t P;
 };
 
+// the host side of it: [round keys: n x 176][H, E_K(J0): n x 32][AAD padded: n x 64]
+static void gcm_host_keys(const uint32_t *ids, size_t n, const uint8_t iv[12], const uint8_t *aad,
+                          size_t aad_len, std::vector<uint8_t> &host) {
+    const size_t rkb = n * 44 * 4, subb = n * 32, aadb = n * 64;
+    host.assign(rkb + subb + aadb, 0);
+    uint32_t *rk = (uint32_t *)host.data();
+    aes128_session_round_keys(ids, n, rk);
+    aes128_gcm_subkeys(rk, n, iv, host.data() + rkb);
+    for (size_t i = 0; i < n && aad_len; ++i)
+        std::memcpy(host.data() + rkb + subb + 64 * i, aad + aad_len * i, aad_len);
+}
+
 static uint32_t gcm_prepare(DeviceCtx *c, const uint32_t *ids, size_t n, size_t ct_bytes,
                             const uint8_t iv[12], const uint8_t *aad, size_t aad_len,
                             std::vector<uint8_t> &host, hipStream_t s, GcmDev &d) {
@@ -184,12 +196,7 @@ static uint32_t gcm_prepare(DeviceCtx *c, const uint32_t *ids, size_t n, size_t 
         !c->gcm_part.reserve(ghash_part_bytes(n, ct_bytes, aad_len) + 16) ||
         !c->gcm_fail.reserve(n * 4 + 16))
         return FLTEE_ERROR_OUT_OF_MEMORY;
-    host.assign(rkb + subb + aadb, 0);
-    uint32_t *rk = (uint32_t *)host.data();
-    aes128_session_round_keys(ids, n, rk);
-    aes128_gcm_subkeys(rk, n, iv, host.data() + rkb);
-    for (size_t i = 0; i < n && aad_len; ++i)
-        std::memcpy(host.data() + rkb + subb + 64 * i, aad + aad_len * i, aad_len);
+    gcm_host_keys(ids, n, iv, aad, aad_len, host);
     if (fl_memcpy_async(c->round_keys.ptr, host.data(), rkb, hipMemcpyHostToDevice, s) != hipSuccess ||
         fl_memcpy_async(c->gcm_sub.ptr, host.data() + rkb, subb + aadb, hipMemcpyHostToDevice, s) != hipSuccess)
         return FLTEE_ERROR_UNEXPECTED;
@@ -646,22 +653,36 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     float *d_out = (float *)c->outbuf.ptr;
     const size_t k_req = num_of_sparse_parameters;
     const float coef = 1.0f / (float)n;
-    // an authenticated upload on a multi-GPU eid: the root alone (GHASH is not sharded)
-    Group *G = aead ? nullptr : group_of(eid);
+    Group *G = group_of(eid);
+    // an authenticated upload over a multi-GPU eid: the call's keys, computed once on the host
+    // (round keys, H || E_K(J0), the AAD padded), for the ranks that verify their shards
+    std::vector<uint8_t> gkeys;
+    GcmHost gh;
+    if (G && aead) {
+        gcm_host_keys(client_ids, n, gcm.iv, gcm.aad.data(), gcm.aad_len, gkeys);
+        gh.sub = gkeys.data() + n * 44 * 4;
+        gh.aad64 = gh.sub + n * 32;
+        gh.iv = gcm.iv;
+        gh.aad_len = gcm.aad_len;
+    }
+    const size_t tagb = aead ? FLTEE_GCM_TAG_BYTES : 0;
     uint32_t st = FLTEE_GROUP_FALLBACK;
     double t2 = 0;
     const bool flat = aggregation_alg == FLTEE_ALG_BASELINE || aggregation_alg == FLTEE_ALG_PATH_ORAM ||
                       aggregation_alg == FLTEE_ALG_NON_OBLIVIOUS;
     const bool tree = ecall_takes_tree(aggregation_alg, n, rpc, d);
-    if (G && flat && !tree && rpc == d && bpc == d * 8) {
+    if (G && flat && !tree && rpc == d && bpc == d * 8 + tagb) {
         // dense uploads over a multi-GPU eid: every GPU loads and decrypts its own
         // parameter range (group.hip); "Loading" = the parallel H2D, "Decryption" = the
-        // decrypt + aggregate + gather
+        // decrypt + aggregate + gather.  Authenticated: every GPU also hashes its range, the
+        // root merges and checks the tags before any GPU aggregates
         std::vector<uint32_t> rk;
-        client_round_keys(client_ids, n, rk);
-        st = group_dense_ecall(G, rk.data(), n, encrypted_parameters_data, d, coef, d_out,
+        if (!aead) client_round_keys(client_ids, n, rk);
+        st = group_dense_ecall(G, aead ? (const uint32_t *)gkeys.data() : rk.data(), n,
+                               encrypted_parameters_data, d, coef, d_out,
                                &execution_time_results[0], &execution_time_results[1],
-                               false);  // out of position: the root's sparse rerun, every alg
+                               false,  // out of position: the root's sparse rerun, every alg
+                               aead ? &gh : nullptr);
         t2 = now_s();
         if (st != FLTEE_SUCCESS && st != FLTEE_GROUP_FALLBACK) return fail(st);
     }
@@ -676,12 +697,14 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     const uint64_t seed = aggregation_alg == FLTEE_ALG_NIPS19 ? next_seed() : 0;
     bool group_tried = false;  // a shape the group declined is not offered to it again
     if (st == FLTEE_GROUP_FALLBACK && sharded && group_splits_host_copy(G)) {
-        // every GPU copies and decrypts the clients of its own position range
+        // every GPU copies and decrypts (authenticated: and verifies) the clients of its own
+        // position range
         std::vector<uint32_t> rk;
-        client_round_keys(client_ids, n, rk);
+        if (!aead) client_round_keys(client_ids, n, rk);
         GroupInput in;
         in.enc = encrypted_parameters_data;
-        in.rk = rk.data();
+        in.rk = aead ? (const uint32_t *)gkeys.data() : rk.data();
+        in.gcm = aead ? &gh : nullptr;
         in.bpc = bpc;
         in.t_load = &execution_time_results[0];
         in.t_dec = &execution_time_results[1];
@@ -793,19 +816,33 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
     if (!c->outbuf.reserve(d * 4 + 16)) return fail(FLTEE_ERROR_OUT_OF_MEMORY);
     d_out = (float *)c->outbuf.ptr;
     uint32_t st;
-    Group *G = aead ? nullptr : group_of(eid);  // authenticated: the root alone
+    Group *G = group_of(eid);
     if (G && group_splits_host_copy(G)) {
-        // the batches split over the eid's GPUs, each loading its own clients (group.hip)
+        // the batches split over the eid's GPUs, each loading (authenticated: and verifying)
+        // its own clients (group.hip)
         std::vector<uint32_t> rk;
-        client_round_keys(client_ids, n, rk);
+        std::vector<uint8_t> gkeys;
+        GcmHost gh;
         GroupInput in;
+        if (aead) {
+            gcm_host_keys(client_ids, n, gcm.iv, gcm.aad.data(), gcm.aad_len, gkeys);
+            gh.sub = gkeys.data() + n * 44 * 4;
+            gh.aad64 = gh.sub + n * 32;
+            gh.iv = gcm.iv;
+            gh.aad_len = gcm.aad_len;
+            in.rk = (const uint32_t *)gkeys.data();
+            in.gcm = &gh;
+        } else {
+            client_round_keys(client_ids, n, rk);
+            in.rk = rk.data();
+        }
         in.enc = encrypted_parameters_data_ptr;
-        in.rk = rk.data();
-        in.bpc = k * 8;
+        in.bpc = bpc6;
         in.t_load = &t_load;
         in.t_dec = &t_dec;
         st = group_optimized(G, in, n, k, d, optimal_num_of_clients, 1.0f / (float)n, d_out, halo6);
         execution_time_results[0] = t_load;
+        if (st == FLTEE_ERROR_MAC_MISMATCH) execution_time_results[1] = t_dec;
     } else if (!G && !aead && n * k * 8 <= kStagedBytes) {
         // one GPU, a small payload: one DMA each way, one host synchronisation
         st = staged_ecall(c, FLTEE_ALG_OPTIMIZED, client_ids, n, encrypted_parameters_data_ptr, k * 8, d,
@@ -937,6 +974,127 @@ extern "C" fltee_status_t fltee_debug_gcm_tag_host(uint32_t client_id, const uin
     aes128_session_round_keys(&client_id, 1, rk);
     aes128_gcm_subkeys(rk, 1, iv, sub);
     gcm_tag_host(sub, sub + 16, aad, aad_len, ct, ct_len, tag);
+    return FLTEE_SUCCESS;
+}
+
+// ---- the pieces of a column-sharded authenticated decrypt (include/fltee_agg.h) ----------
+// a window [16 first_block, 16 first_block + win_bytes) of a slice of ct_bytes: inside the
+// slice, ending on a block boundary or at the slice's end
+static bool gcm_window_ok(size_t ct_bytes, size_t aad_len, size_t first_block, size_t win_bytes) {
+    if (!gcm_sizes_ok(ct_bytes, aad_len)) return false;
+    if (first_block > ct_bytes / 16) return false;  // starts past the slice
+    const size_t lo = first_block * 16;
+    if (win_bytes > ct_bytes - lo) return false;  // reaches past it
+    return win_bytes % 16 == 0 || lo + win_bytes == ct_bytes;
+}
+
+extern "C" size_t fltee_gcm_segments(size_t ct_bytes, size_t aad_len) {
+    return ghash_segments(ct_bytes, aad_len);
+}
+
+extern "C" fltee_status_t fltee_ghash_window_device(const uint32_t *client_ids, size_t n,
+                                                    const void *d_window, size_t row_stride,
+                                                    size_t ct_bytes, size_t first_block,
+                                                    size_t win_bytes, const uint8_t *aad, size_t aad_len,
+                                                    int with_aad, void *d_part, void *stream) {
+    if (!gcm_window_ok(ct_bytes, aad_len, first_block, win_bytes) || row_stride < win_bytes ||
+        (with_aad && aad_len && !aad))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    if (n == 0) return FLTEE_SUCCESS;
+    if (!client_ids || !d_part || (win_bytes && !d_window)) return FLTEE_ERROR_INVALID_PARAMETER;
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    DeviceCtx *c = current_ctx();
+    if (!c) return FLTEE_ERROR_INVALID_PARAMETER;
+    hipStream_t s = (hipStream_t)stream;
+    if (!c->gcm_sub.reserve(n * 96) || !c->gcm_pow.reserve(ghash_pow_bytes(n))) return FLTEE_ERROR_OUT_OF_MEMORY;
+    // H needs no IV (E_K(J0), computed beside it, is not read here)
+    static const uint8_t zero_iv[12] = {};
+    std::vector<uint8_t> host;
+    gcm_host_keys(client_ids, n, zero_iv, with_aad ? aad : nullptr, with_aad ? aad_len : 0, host);
+    const uint8_t *sub = (const uint8_t *)c->gcm_sub.ptr;
+    if (fl_memcpy_async(c->gcm_sub.ptr, host.data() + n * 44 * 4, n * 96, hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_ghash_powers(sub, n, c->gcm_pow.ptr, s) != hipSuccess ||
+        launch_ghash_window((const uint8_t *)d_window, n, row_stride, ct_bytes, first_block, win_bytes,
+                            sub + n * 32, aad_len, with_aad != 0, c->gcm_pow.ptr, d_part, s) != hipSuccess)
+        return FLTEE_ERROR_UNEXPECTED;
+    // the staged keys live on this stack frame
+    return fl_stream_sync(s) == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_ghash_merge_device(void *d_acc, const void *d_part, size_t n, size_t P,
+                                                   void *stream) {
+    if (n == 0 || P == 0) return FLTEE_SUCCESS;
+    if (!d_acc || !d_part || (uintptr_t)d_acc % 16 || (uintptr_t)d_part % 16 || P > SIZE_MAX / 16 / n)
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    return launch_ghash_merge(d_acc, d_part, n, P, (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_gcm_finish_device(const uint32_t *client_ids, size_t n, const void *d_part,
+                                                  size_t ct_bytes, const uint8_t iv[12], size_t aad_len,
+                                                  const void *d_tags, uint32_t *d_fail, void *stream) {
+    if (!gcm_sizes_ok(ct_bytes, aad_len) || !iv) return FLTEE_ERROR_INVALID_PARAMETER;
+    if (n == 0) return FLTEE_SUCCESS;
+    if (!client_ids || !d_part || !d_tags || !d_fail) return FLTEE_ERROR_INVALID_PARAMETER;
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    DeviceCtx *c = current_ctx();
+    if (!c) return FLTEE_ERROR_INVALID_PARAMETER;
+    hipStream_t s = (hipStream_t)stream;
+    if (!c->gcm_sub.reserve(n * 96) || !c->gcm_pow.reserve(ghash_pow_bytes(n))) return FLTEE_ERROR_OUT_OF_MEMORY;
+    std::vector<uint8_t> host;
+    gcm_host_keys(client_ids, n, iv, nullptr, 0, host);
+    const uint8_t *sub = (const uint8_t *)c->gcm_sub.ptr;
+    if (fl_memcpy_async(c->gcm_sub.ptr, host.data() + n * 44 * 4, n * 32, hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_ghash_powers(sub, n, c->gcm_pow.ptr, s) != hipSuccess ||
+        launch_ghash_finish_tags((uint8_t *)const_cast<void *>(d_tags), FLTEE_GCM_TAG_BYTES, n, ct_bytes,
+                                 aad_len, sub, c->gcm_pow.ptr, d_part, false, d_fail, c->status,
+                                 s) != hipSuccess)
+        return FLTEE_ERROR_UNEXPECTED;
+    return fl_stream_sync(s) == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_decrypt_slice_auth_device(const uint32_t *client_ids, size_t n,
+                                                          const void *d_window, size_t row_stride,
+                                                          size_t first_block, size_t win_bytes,
+                                                          const uint8_t iv[12], void *d_records,
+                                                          void *stream) {
+    // the window's last counter is 1 + first_block + ceil(win_bytes / 16): within 32 bits
+    const uint64_t lim = ((uint64_t)1 << 36) - 32;
+    if (!iv || row_stride < win_bytes || (uint64_t)first_block > lim / 16 ||
+        (uint64_t)win_bytes > lim - 16 * (uint64_t)first_block)
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    if (n == 0 || win_bytes < 8) return FLTEE_SUCCESS;
+    if (!client_ids || !d_window || !d_records) return FLTEE_ERROR_INVALID_PARAMETER;
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    DeviceCtx *c = current_ctx();
+    if (!c) return FLTEE_ERROR_INVALID_PARAMETER;
+    hipStream_t s = (hipStream_t)stream;
+    if (!c->round_keys.reserve(n * 44 * 4)) return FLTEE_ERROR_OUT_OF_MEMORY;
+    std::vector<uint32_t> rk(n * 44);
+    aes128_session_round_keys(client_ids, n, rk.data());
+    const size_t rpc = win_bytes / 8;
+    if (fl_memcpy_async(c->round_keys.ptr, rk.data(), rk.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_aes_ctr_gcm_slice((const uint8_t *)d_window, n, row_stride, rpc,
+                                 (const uint32_t *)c->round_keys.ptr, (uint8_t *)d_records, rpc * 8, iv,
+                                 first_block, 0, s) != hipSuccess)
+        return FLTEE_ERROR_UNEXPECTED;
+    return fl_stream_sync(s) == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_debug_ghash_window_host(uint32_t client_id, const uint8_t *aad,
+                                                        size_t aad_len, int with_aad,
+                                                        const uint8_t *ct_window, size_t ct_bytes,
+                                                        size_t first_block, size_t win_bytes,
+                                                        uint8_t *part_out) {
+    if (!gcm_window_ok(ct_bytes, aad_len, first_block, win_bytes) || !part_out ||
+        (with_aad && aad_len && !aad) || (win_bytes && !ct_window))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    static const uint8_t zero_iv[12] = {};
+    uint32_t rk[44];
+    uint8_t sub[32];
+    aes128_session_round_keys(&client_id, 1, rk);
+    aes128_gcm_subkeys(rk, 1, zero_iv, sub);
+    ghash_window_host(sub, aad, aad_len, with_aad != 0, ct_window, ct_bytes, first_block, win_bytes, part_out);
     return FLTEE_SUCCESS;
 }
 

@@ -64,6 +64,9 @@ struct Rank {
     ncclComm_t comm = nullptr;
     Buffer cipher, rec, rk, out, chunk, spare, fold, fold_dst, cbuf, ctmp, lap, list, cnt, st;
     Buffer side, tot;  // advanced's fold: side records; its total, then the totals before it
+    // authenticated uploads: H || E_K(J0) and the AAD of the rank's clients, the powers of H,
+    // the GHASH partials, the fail words (the auth word behind them)
+    Buffer gsub, gpow, gpart, gfail;
 };
 
 struct Group {
@@ -71,6 +74,7 @@ struct Group {
     bool rccl = false;
     std::vector<Rank> r;
     Buffer rows;                    // root: W x d reduce rows (virtual ranks) / alg-6 batch rows
+    Buffer gparts, gtags;           // root: the ranks' GHASH partials (W x n x P x 16), the n tags
     uint32_t *host = nullptr;       // pinned readback words
 };
 
@@ -181,7 +185,8 @@ static void group_free(Group *G) {
         if (hipSetDevice(R.dev) != hipSuccess) continue;
         if (R.s && (G->rccl || i == 0)) (void)fl_stream_sync(R.s);
         for (Buffer *b : {&R.cipher, &R.rec, &R.rk, &R.out, &R.chunk, &R.spare, &R.fold, &R.fold_dst,
-                          &R.cbuf, &R.ctmp, &R.lap, &R.list, &R.cnt, &R.st})
+                          &R.cbuf, &R.ctmp, &R.lap, &R.list, &R.cnt, &R.st, &R.gsub, &R.gpow, &R.gpart,
+                          &R.gfail})
             b->release();
         if (R.comm) (void)rccl()->CommDestroy(R.comm);
         R.comm = nullptr;
@@ -190,6 +195,8 @@ static void group_free(Group *G) {
     }
     if (!G->r.empty() && hipSetDevice(G->r[0].dev) == hipSuccess) {
         G->rows.release();
+        G->gparts.release();
+        G->gtags.release();
         if (G->host) (void)hipHostFree(G->host);
         G->host = nullptr;
     }
@@ -365,6 +372,8 @@ static uint32_t group_records(Group &G, const GroupInput &in, size_t n, size_t r
         c_lo[i] = rpc ? a / rpc : 0;
         c_hi[i] = (rpc && b > a) ? (b + rpc - 1) / rpc : c_lo[i];
     }
+    const GcmHost *g = in.gcm;
+    const size_t ctb = g ? in.bpc - FLTEE_GCM_TAG_BYTES : in.bpc;  // ciphertext bytes per client
     const auto t0 = std::chrono::steady_clock::now();
     auto load = [&](int i) {
         Rank &R = G.r[i];
@@ -372,6 +381,16 @@ static uint32_t group_records(Group &G, const GroupInput &in, size_t n, size_t r
         if (hipSetDevice(R.dev) != hipSuccess) { errs[i] = 1; return; }
         if (!R.cipher.reserve(nc * in.bpc + 16) || !R.rec.reserve(nc * rpc * 8 + 16) ||
             !R.rk.reserve(nc * 44 * 4 + 16)) { errs[i] = 3; return; }
+        if (g) {  // the rank's clients' subkeys and AAD; its auth word (behind the fail words) = 0
+            if (!R.gsub.reserve(nc * 96 + 16) || !R.gpow.reserve(ghash_pow_bytes(nc) + 16) ||
+                !R.gpart.reserve(ghash_part_bytes(nc, ctb, g->aad_len) + 16) ||
+                !R.gfail.reserve(nc * 4 + 16)) { errs[i] = 3; return; }
+            if (fl_memset_async((uint32_t *)R.gfail.ptr + nc, 0, 4, R.s) != hipSuccess ||
+                (nc && (fl_memcpy_async(R.gsub.ptr, g->sub + c_lo[i] * 32, nc * 32, hipMemcpyHostToDevice,
+                                        R.s) != hipSuccess ||
+                        fl_memcpy_async((uint8_t *)R.gsub.ptr + nc * 32, g->aad64 + c_lo[i] * 64, nc * 64,
+                                        hipMemcpyHostToDevice, R.s) != hipSuccess))) { errs[i] = 1; return; }
+        }
         if (nc == 0) return;
         if (fl_memcpy_async(R.rk.ptr, in.rk + c_lo[i] * 44, nc * 44 * 4, hipMemcpyHostToDevice, R.s) != hipSuccess ||
             fl_memcpy_async(R.cipher.ptr, in.enc + c_lo[i] * in.bpc, nc * in.bpc, hipMemcpyHostToDevice,
@@ -396,14 +415,37 @@ static uint32_t group_records(Group &G, const GroupInput &in, size_t n, size_t r
         const size_t nc = c_hi[i] - c_lo[i];
         rec_r[i] = (const uint64_t *)R.rec.ptr + (lo[i] < nrec ? lo[i] - c_lo[i] * rpc : 0);
         if (nc == 0) continue;
-        if (hipSetDevice(R.dev) != hipSuccess ||
-            launch_aes_ctr((const uint8_t *)R.cipher.ptr, nc, in.bpc, rpc, (const uint32_t *)R.rk.ptr,
+        if (hipSetDevice(R.dev) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+        if (g) {  // whole slices: the one-GPU kernels on the rank's clients
+            const uint8_t *ct = (const uint8_t *)R.cipher.ptr, *sub = (const uint8_t *)R.gsub.ptr;
+            uint32_t *fail = (uint32_t *)R.gfail.ptr;
+            if (launch_ghash_powers(sub, nc, R.gpow.ptr, R.s) != hipSuccess ||
+                launch_aes_ctr_gcm(ct, nc, in.bpc, rpc, (const uint32_t *)R.rk.ptr, (uint8_t *)R.rec.ptr,
+                                   rpc * 8, g->iv, R.s) != hipSuccess ||
+                launch_ghash_bulk(ct, nc, in.bpc, ctb, sub + nc * 32, g->aad_len, R.gpow.ptr, R.gpart.ptr,
+                                  R.s) != hipSuccess ||
+                launch_ghash_finish(const_cast<uint8_t *>(ct), nc, in.bpc, ctb, g->aad_len, sub, R.gpow.ptr,
+                                    R.gpart.ptr, false, fail, fail + nc, R.s) != hipSuccess)
+                return FLTEE_ERROR_UNEXPECTED;
+            continue;
+        }
+        if (launch_aes_ctr((const uint8_t *)R.cipher.ptr, nc, in.bpc, rpc, (const uint32_t *)R.rk.ptr,
                            (uint8_t *)R.rec.ptr, R.s) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
     }
-    if (sync_all(G) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+    // the W verdicts, before the caller builds or sorts anything
+    std::vector<uint32_t> auth;
+    if (g) {
+        std::vector<const uint32_t *> aw;
+        for (int i = 0; i < W; ++i) aw.push_back((const uint32_t *)G.r[i].gfail.ptr + (c_hi[i] - c_lo[i]));
+        if (read_words(G, aw, auth)) return FLTEE_ERROR_UNEXPECTED;
+    } else if (sync_all(G) != hipSuccess) {
+        return FLTEE_ERROR_UNEXPECTED;
+    }
     if (in.t_load) *in.t_load = std::chrono::duration<float>(t1 - t0).count();
     if (in.t_dec) *in.t_dec = std::chrono::duration<float>(std::chrono::steady_clock::now() - t1).count();
+    for (uint32_t v : auth)
+        if (v) return FLTEE_ERROR_MAC_MISMATCH;
     return FLTEE_SUCCESS;
 }
 
@@ -411,14 +453,23 @@ static uint32_t group_records(Group &G, const GroupInput &in, size_t n, size_t r
 // Parameter-range shard of dense uploads, straight from the host ciphertext.
 uint32_t group_dense_ecall(Group *Gp, const uint32_t *rk_host, size_t n, const uint8_t *enc,
                            size_t d, float coef, float *d_out_root, float *t_load, float *t_dec,
-                           bool reject_order) {
+                           bool reject_order, const GcmHost *gcm) {
     Group &G = *Gp;
     const int W = G.W;
+    if (gcm && d == 0) return FLTEE_GROUP_FALLBACK;  // no rank has a window: the root's call
     std::vector<size_t> p(W + 1);
     // multiples of 4: whole 16-B AES blocks, 16-B aligned output slices
     for (int i = 0; i <= W; ++i) p[i] = (d * (size_t)i / (size_t)W) & ~(size_t)3;
     p[W] = d;
-    const size_t bpc = d * 8;
+    const size_t ctb = d * 8, bpc = ctb + (gcm ? FLTEE_GCM_TAG_BYTES : 0);  // the host stride
+    // authenticated: the ranks' partial vectors (n x P x 16 bytes each) meet on the root, one
+    // slot per rank; a virtual rank's window kernel writes its slot in place
+    const size_t P = gcm ? ghash_segments(ctb, gcm->aad_len) : 0, partb = n * P * 16;
+    int first = 0;  // the first rank with columns: its window starts at block 0 and takes the AAD
+    while (first < W - 1 && p[first + 1] == p[first]) ++first;
+    if (gcm && (!reserve_on(G.r[0], G.gparts, (size_t)W * partb + 16) ||
+                !reserve_on(G.r[0], G.gtags, n * 16 + 16)))
+        return FLTEE_ERROR_OUT_OF_MEMORY;
     std::vector<uint32_t> errs(W, 0);
     auto t0 = std::chrono::steady_clock::now();
     // one host thread per GPU: pageable H2D copies to different GPUs overlap only when
@@ -427,11 +478,23 @@ uint32_t group_dense_ecall(Group *Gp, const uint32_t *rk_host, size_t n, const u
         Rank &R = G.r[i];
         const size_t dg = p[i + 1] - p[i];
         if (hipSetDevice(R.dev) != hipSuccess) { errs[i] = 1; return; }
+        if (gcm && (dg || i == 0)) {  // H, E_K(J0) and the AAD of every client; the root: the tags
+            if (!R.gsub.reserve(n * 96) || !R.gpow.reserve(ghash_pow_bytes(n)) ||
+                !R.gpart.reserve(partb + 16) || !R.gfail.reserve(n * 4 + 16)) { errs[i] = 3; return; }
+            if (fl_memcpy_async(R.gsub.ptr, gcm->sub, n * 96, hipMemcpyHostToDevice, R.s) != hipSuccess ||
+                (i == 0 && (fl_memset_async((uint32_t *)R.gfail.ptr + n, 0, 4, R.s) != hipSuccess ||
+                            fl_memcpy2d_async(G.gtags.ptr, 16, enc + ctb, bpc, 16, n, hipMemcpyHostToDevice,
+                                              R.s) != hipSuccess))) { errs[i] = 1; return; }
+        }
+        // (a rank without columns still answers the status readback below: its word reads 0)
+        if (!R.st.reserve(64)) { errs[i] = 3; return; }
+        if (fl_memset_async(R.st.ptr, 0, 4, R.s) != hipSuccess) { errs[i] = 1; return; }
         if (dg == 0) return;
-        if (!R.cipher.reserve(n * dg * 8) || !R.rec.reserve(n * dg * 8) || !R.rk.reserve(n * 44 * 4) ||
-            !R.st.reserve(64)) { errs[i] = 3; return; }
-        if (fl_memset_async(R.st.ptr, 0, 4, R.s) != hipSuccess ||
-            fl_memcpy_async(R.rk.ptr, rk_host, n * 44 * 4, hipMemcpyHostToDevice, R.s) != hipSuccess ||
+        if (!R.cipher.reserve(n * dg * 8) || !R.rec.reserve(n * dg * 8) || !R.rk.reserve(n * 44 * 4)) {
+            errs[i] = 3;
+            return;
+        }
+        if (fl_memcpy_async(R.rk.ptr, rk_host, n * 44 * 4, hipMemcpyHostToDevice, R.s) != hipSuccess ||
             fl_memcpy2d_async(R.cipher.ptr, dg * 8, enc + p[i] * 8, bpc, dg * 8, n, hipMemcpyHostToDevice,
                              R.s) != hipSuccess) { errs[i] = 1; return; }
     };
@@ -448,22 +511,79 @@ uint32_t group_dense_ecall(Group *Gp, const uint32_t *rk_host, size_t n, const u
     auto t1 = std::chrono::steady_clock::now();
     if (t_load) *t_load = std::chrono::duration<float>(t1 - t0).count();
     std::vector<P2P> gather;
-    for (int i = 0; i < W; ++i) {
+    auto accumulate = [&](int i) -> uint32_t {  // rank i's columns of the n clients, in order
         Rank &R = G.r[i];
         const size_t dg = p[i + 1] - p[i];
-        if (dg == 0) continue;
-        if (hipSetDevice(R.dev) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
         float *o = G.rccl && i ? nullptr : d_out_root + p[i];
         if (!o) {
             if (!R.out.reserve(dg * 4)) return FLTEE_ERROR_OUT_OF_MEMORY;
             o = (float *)R.out.ptr;
             gather.push_back({i, 0, o, d_out_root + p[i], dg * 4});
         }
+        return launch_dense_accumulate(R.rec.ptr, n, dg, coef, o, nullptr, false, (uint32_t *)R.st.ptr,
+                                       R.s) == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+    };
+    for (int i = 0; i < W; ++i) {
+        Rank &R = G.r[i];
+        const size_t dg = p[i + 1] - p[i];
+        if (dg == 0) continue;
+        if (hipSetDevice(R.dev) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+        if (gcm) continue;
         if (launch_aes_ctr_slice((const uint8_t *)R.cipher.ptr, n, dg * 8, dg, (const uint32_t *)R.rk.ptr,
-                                 (uint8_t *)R.rec.ptr, p[i] / 2, (uint32_t)p[i], R.s) != hipSuccess ||
-            launch_dense_accumulate(R.rec.ptr, n, dg, coef, o, nullptr, false, (uint32_t *)R.st.ptr,
-                                    R.s) != hipSuccess)
+                                 (uint8_t *)R.rec.ptr, p[i] / 2, (uint32_t)p[i], R.s) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
+        if (uint32_t st = accumulate(i)) return st;
+    }
+    if (gcm) {
+        // every rank: the powers of H, its columns decrypted with the counters of their blocks,
+        // and its window's partials — into its slot on the root (a real rank: sent there)
+        uint8_t *slots = (uint8_t *)G.gparts.ptr;
+        std::vector<P2P> parts;
+        for (int i = 0; i < W; ++i) {
+            Rank &R = G.r[i];
+            const size_t dg = p[i + 1] - p[i];
+            if (dg == 0 && i) continue;
+            if (hipSetDevice(R.dev) != hipSuccess ||
+                launch_ghash_powers((const uint8_t *)R.gsub.ptr, n, R.gpow.ptr, R.s) != hipSuccess)
+                return FLTEE_ERROR_UNEXPECTED;
+            if (dg == 0) {  // a root without columns still holds the sum
+                if (fl_memset_async(slots, 0, partb, R.s) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+                continue;
+            }
+            uint8_t *part = G.rccl && i ? (uint8_t *)R.gpart.ptr : slots + (size_t)i * partb;
+            if (G.rccl && i) parts.push_back({i, 0, part, slots + (size_t)i * partb, partb});
+            if (launch_aes_ctr_gcm_slice((const uint8_t *)R.cipher.ptr, n, dg * 8, dg,
+                                         (const uint32_t *)R.rk.ptr, (uint8_t *)R.rec.ptr, dg * 8, gcm->iv,
+                                         p[i] / 2, (uint32_t)p[i], R.s) != hipSuccess ||
+                launch_ghash_window((const uint8_t *)R.cipher.ptr, n, dg * 8, ctb, p[i] / 2, dg * 8,
+                                    (const uint8_t *)R.gsub.ptr + n * 32, gcm->aad_len, i == first, R.gpow.ptr,
+                                    part, R.s) != hipSuccess)
+                return FLTEE_ERROR_UNEXPECTED;
+        }
+        if (p2p(G, parts) != hipSuccess || hipSetDevice(G.r[0].dev) != hipSuccess)
+            return FLTEE_ERROR_UNEXPECTED;
+        Rank &R0 = G.r[0];
+        for (int i = 1; i < W; ++i)
+            if (p[i + 1] > p[i] &&
+                launch_ghash_merge(slots, slots + (size_t)i * partb, n, P, R0.s) != hipSuccess)
+                return FLTEE_ERROR_UNEXPECTED;
+        uint32_t *fail = (uint32_t *)R0.gfail.ptr;
+        if (launch_ghash_finish_tags((uint8_t *)G.gtags.ptr, 16, n, ctb, gcm->aad_len,
+                                     (const uint8_t *)R0.gsub.ptr, R0.gpow.ptr, slots, false, fail, fail + n,
+                                     R0.s) != hipSuccess)
+            return FLTEE_ERROR_UNEXPECTED;
+        // the verdict (the read synchronises every rank): nothing is summed before it
+        std::vector<uint32_t> auth;
+        if (read_words(G, {fail + n}, auth)) return FLTEE_ERROR_UNEXPECTED;
+        if (auth[0]) {
+            if (t_dec) *t_dec = std::chrono::duration<float>(std::chrono::steady_clock::now() - t1).count();
+            return FLTEE_ERROR_MAC_MISMATCH;
+        }
+        for (int i = 0; i < W; ++i) {
+            if (p[i + 1] == p[i]) continue;
+            if (hipSetDevice(G.r[i].dev) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+            if (uint32_t st = accumulate(i)) return st;
+        }
     }
     if (p2p(G, gather) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
     std::vector<const uint32_t *> sw;

@@ -647,15 +647,30 @@ hipError_t launch_aes_ctr_slice(const uint8_t *cipher, size_t n, size_t bytes_pe
 
 // GCM's CTR half: keystream block i = E_K(IV || BE32(2 + i)); n slices at in_stride ->
 // rec_per_client records each at out_stride (either side may carry a tag behind its slice)
-hipError_t launch_aes_ctr_gcm(const uint8_t *in, size_t n, size_t in_stride, size_t rec_per_client,
-                              const uint32_t *round_keys, uint8_t *out, size_t out_stride,
-                              const uint8_t iv[12], hipStream_t s, uint32_t *zero_word) {
+static GcmIv gcm_iv_words(const uint8_t iv[12]) {
     GcmIv w;
     for (int j = 0; j < 3; ++j)
         w.w[j] = ((uint32_t)iv[4 * j] << 24) | ((uint32_t)iv[4 * j + 1] << 16) |
                  ((uint32_t)iv[4 * j + 2] << 8) | iv[4 * j + 3];
+    return w;
+}
+
+hipError_t launch_aes_ctr_gcm(const uint8_t *in, size_t n, size_t in_stride, size_t rec_per_client,
+                              const uint32_t *round_keys, uint8_t *out, size_t out_stride,
+                              const uint8_t iv[12], hipStream_t s, uint32_t *zero_word) {
     return launch_ctr<true>(in, n, in_stride, rec_per_client, round_keys, out, 2, 0, s, zero_word,
-                            out_stride, w);
+                            out_stride, gcm_iv_words(iv));
+}
+
+// A column shard of GCM slices: the rows hold the blocks from first_block on, so the kernels'
+// block offset (the counter of a row's first block, folded into the counter planes) is
+// 2 + first_block: both of launch_aes_ctr_slice's offsets and launch_aes_ctr_gcm's IV.
+hipError_t launch_aes_ctr_gcm_slice(const uint8_t *in, size_t n, size_t in_stride, size_t rec_per_client,
+                                    const uint32_t *round_keys, uint8_t *out, size_t out_stride,
+                                    const uint8_t iv[12], uint64_t first_block, uint32_t idx_sub,
+                                    hipStream_t s) {
+    return launch_ctr<true>(in, n, in_stride, rec_per_client, round_keys, out, 2 + first_block,
+                            idx_sub, s, nullptr, out_stride, gcm_iv_words(iv));
 }
 
 hipError_t launch_aes_ctr(const uint8_t *cipher, size_t n, size_t bytes_per_client,

@@ -31,7 +31,20 @@
 //                         FLTEE_DEV_ERR_AUTH into the status word, no early exit, and the
 //                         computed tag stays in registers.  Emit (the client producer):
 //                         the tag is written behind the ciphertext.
-// Every size, grid and loop bound is a function of (n, B, |AAD|) only.
+//   ghash_window_kernel the bulk kernel on a WINDOW of every slice (a multi-GPU eid's column
+//                         shard, group.hip): a rank holds the ciphertext blocks [first_block,
+//                         first_block + ceil(win_bytes / 16)) of each client at a row stride
+//                         of its own and writes part_s in the WHOLE slice's segment layout.
+//                         part_s is XOR-linear in the segment's blocks, so blocks outside the
+//                         window count as zero and the XOR of the ranks' partial vectors
+//                         (ghash_merge_kernel, 16-B lanes) is the slice's, bit for bit.  Only
+//                         the segments the window (and, on the one window that carries them,
+//                         the AAD blocks) touches are launched — an untouched segment would
+//                         cost its S multiplies for a zero — and the others are a memset;
+//                         inside a touched segment the blocks before and behind the window are
+//                         masked by position (v_cmp / v_cndmask on public values).
+// Every size, grid and loop bound is a function of (n, B, |AAD|) — for a window, of (n, B,
+// |AAD|, first_block, win_bytes) — only.
 #include <vector>
 
 #include "common.h"
@@ -82,6 +95,37 @@ void gcm_tag_host(const uint8_t h[16], const uint8_t ej0[16], const uint8_t *aad
     for (int j = 0; j < 4; ++j) {
         const uint32_t v = gf128_le_word(y, j);
         for (int i = 0; i < 4; ++i) tag[4 * j + i] = (uint8_t)(v >> (8 * i)) ^ ej0[4 * j + i];
+    }
+}
+
+// One window's partial vector on the host, block after block with the same multiply: part_s =
+// sum over the window's (and, with_aad, the AAD's) virtual blocks j of segment s of
+// x_j H^(S - j mod S); ct_window holds the window's win_bytes bytes
+void ghash_window_host(const uint8_t h[16], const uint8_t *aad, size_t aad_len, bool with_aad,
+                       const uint8_t *ct_window, size_t ct_bytes, uint64_t first_block,
+                       size_t win_bytes, uint8_t *part_out) {
+    const gf128 H = gf128_from_bytes(h);
+    const uint64_t P = ghash_segments(ct_bytes, aad_len), ab = (aad_len + 15) / 16;
+    const uint64_t pad = P * kGhashSeg - ((ct_bytes + 15) / 16 + ab);
+    auto block = [&](uint64_t v) {
+        uint8_t blk[16] = {};
+        if (v >= pad && v - pad < ab) {
+            const size_t o = 16 * (v - pad);
+            for (size_t i = 0; with_aad && i < 16 && o + i < aad_len; ++i) blk[i] = aad[o + i];
+        } else if (v >= pad + ab && v - pad - ab >= first_block) {
+            const uint64_t o = 16 * (v - pad - ab - first_block);
+            for (size_t i = 0; i < 16 && o + i < win_bytes; ++i) blk[i] = ct_window[o + i];
+        }
+        return gf128_from_bytes(blk);
+    };
+    for (uint64_t s = 0; s < P; ++s) {
+        gf128 y = gf128_zero();  // Horner over the segment: ends with every block times H^(S - j)
+        for (uint64_t j = 0; j < (uint64_t)kGhashSeg; ++j)
+            y = gf128_mul(gf128_xor(y, block(s * kGhashSeg + j)), H);
+        // as the kernels store a partial: the element's words (every byte of the GCM block
+        // with its bits reversed)
+        for (int j = 0; j < 4; ++j)
+            for (int i = 0; i < 4; ++i) part_out[16 * s + 4 * j + i] = (uint8_t)(y.w[j] >> (8 * i));
     }
 }
 
@@ -194,9 +238,94 @@ __global__ __launch_bounds__(256) void ghash_bulk_kernel(const uint8_t *__restri
     }
 }
 
-// EMIT: write the tag behind the ciphertext; else compare with the one received there
+// the virtual block v of a client's slice as one window of it sees it: zero in front of the
+// slice, outside the window, and (unless this window carries them) on the AAD blocks; the
+// window's last block zero padded (a window ends off a block boundary only at ct_bytes)
+template <int ALIGN>
+__device__ __forceinline__ gf128 ghash_window_block(uint64_t v, uint64_t pad, uint32_t ablocks,
+                                                    bool with_aad, const uint8_t *__restrict__ aad,
+                                                    const uint8_t *__restrict__ win,
+                                                    uint64_t first_block, uint64_t win_bytes) {
+    if (v < pad) return gf128_zero();
+    const uint64_t t = v - pad;
+    if (t < ablocks) {
+        if (!with_aad) return gf128_zero();
+        const uint4 q = *reinterpret_cast<const uint4 *>(aad + 16 * t);
+        return gf128_from_le_words(q.x, q.y, q.z, q.w);
+    }
+    const uint64_t cb = t - ablocks;
+    if (cb < first_block) return gf128_zero();
+    const uint64_t o = 16 * (cb - first_block);
+    if (o >= win_bytes) return gf128_zero();
+    const uint8_t *p = win + o;
+    if (o + 16 <= win_bytes) {
+        if (ALIGN == 16) {
+            const uint4 q = *reinterpret_cast<const uint4 *>(p);
+            return gf128_from_le_words(q.x, q.y, q.z, q.w);
+        }
+        if (ALIGN == 8) {
+            const uint2 q0 = *reinterpret_cast<const uint2 *>(p);
+            const uint2 q1 = *reinterpret_cast<const uint2 *>(p + 8);
+            return gf128_from_le_words(q0.x, q0.y, q1.x, q1.y);
+        }
+        return gf128_from_bytes(p);
+    }
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    for (int i = 0; i < 16; ++i)
+        if (o + i < win_bytes) w[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
+    return gf128_from_le_words(w[0], w[1], w[2], w[3]);
+}
+
+// one wave per (client, segment s0 + j), j < ns: the bulk kernel's chain on the window's view
+// of the segment; pad and P are the whole slice's
+template <int ALIGN>
+__global__ __launch_bounds__(256) void ghash_window_kernel(const uint8_t *__restrict__ window,
+                                                           size_t stride, uint64_t first_block,
+                                                           uint64_t win_bytes, uint64_t pad,
+                                                           const uint8_t *__restrict__ aad,
+                                                           uint32_t ablocks, bool with_aad,
+                                                           const gf128 *__restrict__ pow,
+                                                           gf128 *__restrict__ part, uint64_t P,
+                                                           uint64_t s0, uint64_t ns, uint64_t waves) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint64_t gw = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); gw < waves;
+         gw += (uint64_t)gridDim.x * 4) {
+        const uint64_t c = gw / ns, s = s0 + (gw - c * ns);
+        const uint8_t *win = window + c * stride;
+        const uint8_t *ad = aad + c * kGhashAadBytes;
+        const gf128 *pw = pow + c * kGhashPow;
+        gf128 x[kGhashChain];
+#pragma unroll
+        for (int r = 0; r < kGhashChain; ++r)
+            x[r] = ghash_window_block<ALIGN>(s * kGhashSeg + 64 * r + lane, pad, ablocks, with_aad, ad,
+                                             win, first_block, win_bytes);
+        const gf128 h64 = pw[64];
+        gf128 y = x[0];
+#pragma unroll 1
+        for (int r = 1; r < kGhashChain; ++r) {
+            y = gf128_xor(gf128_mul(y, h64), x[1]);
+#pragma unroll
+            for (int i = 1; i + 1 < kGhashChain; ++i) x[i] = x[i + 1];  // the next block first
+        }
+        y = wave_xor(gf128_mul(y, pw[64 - lane]));
+        if (lane == 0) part[c * P + s] = y;
+    }
+}
+
+// acc ^= part, 16 bytes per lane: the ranks' partial vectors into the root's
+__global__ __launch_bounds__(256) void ghash_merge_kernel(uint4 *__restrict__ acc,
+                                                          const uint4 *__restrict__ part, size_t n16) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) {
+        const uint4 a = acc[i], b = part[i];
+        acc[i] = make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
+    }
+}
+
+
+// EMIT: write the tag at tags + c * tag_stride (behind the ciphertext); else compare with the
+// one received there (a column shard's tags lie in a buffer of their own, n x 16 bytes)
 template <bool EMIT>
-__global__ __launch_bounds__(64) void ghash_finish_kernel(uint8_t *__restrict__ cipher, size_t stride,
+__global__ __launch_bounds__(64) void ghash_finish_kernel(uint8_t *__restrict__ tags, size_t tag_stride,
                                                           uint64_t ct_bytes, uint64_t aad_len,
                                                           const uint8_t *__restrict__ sub,
                                                           const gf128 *__restrict__ pow,
@@ -218,7 +347,7 @@ __global__ __launch_bounds__(64) void ghash_finish_kernel(uint8_t *__restrict__ 
     }
     y = wave_xor(gf128_mul(y, gp[63 - lane]));
     y = gf128_mul(gf128_xor(y, gf128_lengths(aad_len, ct_bytes)), pw[1]);
-    uint8_t *tagp = cipher + (size_t)c * stride + ct_bytes;
+    uint8_t *tagp = tags + (size_t)c * tag_stride;
     const uint8_t *ej0 = sub + (size_t)c * 32 + 16;
     uint32_t diff = 0;
 #pragma unroll
@@ -273,20 +402,81 @@ hipError_t launch_ghash_bulk(const uint8_t *cipher, size_t n, size_t stride, siz
     return hipGetLastError();
 }
 
-hipError_t launch_ghash_finish(uint8_t *cipher, size_t n, size_t stride, size_t ct_bytes,
-                               size_t aad_len, const uint8_t *sub, const void *pow, const void *part,
-                               bool emit, uint32_t *fail, uint32_t *status, hipStream_t s) {
+// the window [first_block, first_block + ceil(win_bytes / 16)) of every slice, n rows at
+// `stride`: part (n x P, the whole slice's layout) = zeros but for the segments the window
+// (with_aad: and the AAD blocks) touches.  The caller has checked the window against the slice.
+hipError_t launch_ghash_window(const uint8_t *window, size_t n, size_t stride, size_t ct_bytes,
+                               uint64_t first_block, size_t win_bytes, const uint8_t *aad,
+                               size_t aad_len, bool with_aad, const void *pow, void *part,
+                               hipStream_t s) {
+    const uint64_t P = ghash_segments(ct_bytes, aad_len);
+    if (n == 0 || P == 0) return hipSuccess;
+    const hipError_t e = fl_memset_async(part, 0, n * P * sizeof(gf128), s);
+    if (e != hipSuccess) return e;
+    const uint32_t ab = (uint32_t)((aad_len + 15) / 16);
+    const uint64_t pad = P * kGhashSeg - ((ct_bytes + 15) / 16 + ab);
+    const uint64_t wb = ((uint64_t)win_bytes + 15) / 16;
+    // virtual blocks [lo, hi): the window's, and in front of them the AAD's where carried
+    uint64_t lo = pad + ab + first_block, hi = lo + wb;
+    if (with_aad && ab) {
+        if (wb == 0) lo = pad, hi = pad + ab;
+        else lo = pad;  // (a window that carries the AAD away from block 0: the hull)
+    }
+    if (hi == lo) return hipSuccess;
+    const uint64_t s0 = lo / kGhashSeg, ns = (hi - 1) / kGhashSeg - s0 + 1, waves = (uint64_t)n * ns;
+    uint64_t blocks = (waves + 3) / 4;
+    if (blocks > 32768) blocks = 32768;  // grid-stride beyond
+    const int align = ((uintptr_t)window % 16 == 0 && stride % 16 == 0) ? 16
+                    : ((uintptr_t)window % 8 == 0 && stride % 8 == 0)   ? 8 : 1;
+    if (align == 16)
+        FLTEE_LAUNCH(ghash_window_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, s, window, stride,
+                     first_block, (uint64_t)win_bytes, pad, aad, ab, with_aad, (const gf128 *)pow,
+                     (gf128 *)part, P, s0, ns, waves);
+    else if (align == 8)
+        FLTEE_LAUNCH(ghash_window_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, s, window, stride,
+                     first_block, (uint64_t)win_bytes, pad, aad, ab, with_aad, (const gf128 *)pow,
+                     (gf128 *)part, P, s0, ns, waves);
+    else
+        FLTEE_LAUNCH(ghash_window_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, window, stride,
+                     first_block, (uint64_t)win_bytes, pad, aad, ab, with_aad, (const gf128 *)pow,
+                     (gf128 *)part, P, s0, ns, waves);
+    return hipGetLastError();
+}
+
+// acc ^= part over n x P partials (both 16-byte aligned)
+hipError_t launch_ghash_merge(void *acc, const void *part, size_t n, size_t P, hipStream_t s) {
+    const size_t n16 = n * P;
+    if (n16 == 0) return hipSuccess;
+    size_t blocks = (n16 + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    FLTEE_LAUNCH(ghash_merge_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (uint4 *)acc,
+                 (const uint4 *)part, n16);
+    return hipGetLastError();
+}
+
+// tags: client c's tag at tags + c * tag_stride (emit: written there)
+hipError_t launch_ghash_finish_tags(uint8_t *tags, size_t tag_stride, size_t n, size_t ct_bytes,
+                                    size_t aad_len, const uint8_t *sub, const void *pow,
+                                    const void *part, bool emit, uint32_t *fail, uint32_t *status,
+                                    hipStream_t s) {
     if (n == 0) return hipSuccess;
     const uint64_t P = ghash_segments(ct_bytes, aad_len);
     if (emit)
-        FLTEE_LAUNCH(ghash_finish_kernel<true>, dim3((unsigned)n), dim3(64), 0, s, cipher, stride,
+        FLTEE_LAUNCH(ghash_finish_kernel<true>, dim3((unsigned)n), dim3(64), 0, s, tags, tag_stride,
                      (uint64_t)ct_bytes, (uint64_t)aad_len, sub, (const gf128 *)pow,
                      (const gf128 *)part, P, fail, status);
     else
-        FLTEE_LAUNCH(ghash_finish_kernel<false>, dim3((unsigned)n), dim3(64), 0, s, cipher, stride,
+        FLTEE_LAUNCH(ghash_finish_kernel<false>, dim3((unsigned)n), dim3(64), 0, s, tags, tag_stride,
                      (uint64_t)ct_bytes, (uint64_t)aad_len, sub, (const gf128 *)pow,
                      (const gf128 *)part, P, fail, status);
     return hipGetLastError();
+}
+
+hipError_t launch_ghash_finish(uint8_t *cipher, size_t n, size_t stride, size_t ct_bytes,
+                               size_t aad_len, const uint8_t *sub, const void *pow, const void *part,
+                               bool emit, uint32_t *fail, uint32_t *status, hipStream_t s) {
+    return launch_ghash_finish_tags(cipher + ct_bytes, stride, n, ct_bytes, aad_len, sub, pow, part,
+                                    emit, fail, status, s);
 }
 
 }  // namespace fltee

@@ -79,6 +79,12 @@ SIGNATURES = {
     "fltee_decrypt_auth_device": (_U32, [_P, _S, _P, _S, _P, _P, _S, _P, _P, _P]),
     "fltee_encrypt_auth_device": (_U32, [_P, _S, _P, _S, _P, _P, _S, _P, _P]),
     "fltee_debug_gcm_tag_host": (_U32, [_U32, _P, _P, _S, _P, _S, _P]),
+    "fltee_gcm_segments": (_S, [_S, _S]),
+    "fltee_ghash_window_device": (_U32, [_P, _S, _P, _S, _S, _S, _S, _P, _S, ctypes.c_int, _P, _P]),
+    "fltee_ghash_merge_device": (_U32, [_P, _P, _S, _S, _P]),
+    "fltee_gcm_finish_device": (_U32, [_P, _S, _P, _S, _P, _S, _P, _P, _P]),
+    "fltee_decrypt_slice_auth_device": (_U32, [_P, _S, _P, _S, _S, _S, _P, _P, _P]),
+    "fltee_debug_ghash_window_host": (_U32, [_U32, _P, _S, ctypes.c_int, _P, _S, _S, _S, _P]),
     "fltee_set_upload_aead": (None, [ctypes.c_int]),
     "fltee_device_status": (_U32, [_P, _P]),
     "fltee_sum_rows_device": (_U32, [_P, _S, _S, _F, _P, _P]),

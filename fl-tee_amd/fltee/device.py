@@ -136,6 +136,72 @@ def decrypt_auth(client_ids, cipher, ct_bytes, iv, aad=b"", records=None, stream
     return records[:n * (ct_bytes // 8)], fail[:n]
 
 
+def gcm_segments(ct_bytes, aad_len):
+    """fltee_gcm_segments: GHASH partials per client of a slice of ct_bytes with aad_len of AAD."""
+    return L.lib().fltee_gcm_segments(ct_bytes, aad_len)
+
+
+def ghash_window(client_ids, window, row_stride, ct_bytes, first_block, win_bytes, aad=b"",
+                 aad_len=None, with_aad=False, part=None, stream=None):
+    """fltee_ghash_window_device: the GHASH partials (uint8 [n, P, 16]) of one window of n
+    slices — ciphertext blocks [first_block, first_block + ceil(win_bytes / 16)) of each, rows
+    of `window` at row_stride bytes.  aad_len is the slices' AAD length (it shapes the segment
+    layout); aad (n x aad_len bytes) is hashed by the one window that passes with_aad."""
+    ids = np.ascontiguousarray(client_ids, dtype=np.uint32)
+    n = len(ids)
+    if aad_len is None:
+        aad_len = len(aad) // max(n, 1)
+    P = gcm_segments(ct_bytes, aad_len)
+    if part is None:
+        part = torch.empty((n, P, 16), dtype=torch.uint8, device=window.device)
+    aadb = (ctypes.c_uint8 * max(len(aad), 1))(*aad)
+    _check(L.lib().fltee_ghash_window_device(ids.ctypes.data_as(ctypes.c_void_p), n, _ptr(window),
+                                             row_stride, ct_bytes, first_block, win_bytes, aadb, aad_len,
+                                             1 if with_aad else 0, _ptr(part), _stream(stream)),
+           "fltee_ghash_window_device")
+    return part
+
+
+def ghash_merge(acc, part, stream=None):
+    """fltee_ghash_merge_device: acc ^= part (two [n, P, 16] partial vectors)."""
+    assert acc.shape == part.shape and acc.is_contiguous() and part.is_contiguous()
+    n, P = acc.shape[0], acc.shape[1]
+    _check(L.lib().fltee_ghash_merge_device(_ptr(acc), _ptr(part), n, P, _stream(stream)),
+           "fltee_ghash_merge_device")
+    return acc
+
+
+def gcm_finish(client_ids, part, ct_bytes, iv, aad_len, tags, stream=None):
+    """fltee_gcm_finish_device: the merged partials against the n received tags (uint8 [n, 16])
+    -> fail (int32 [n], 1 where a tag did not verify; FLTEE_DEV_ERR_AUTH then in the status)."""
+    ids = np.ascontiguousarray(client_ids, dtype=np.uint32)
+    n = len(ids)
+    assert len(iv) == 12 and tags.is_contiguous()
+    fail = torch.full((max(n, 1),), 0x7fffffff, dtype=torch.int32, device=part.device)
+    ivb = (ctypes.c_uint8 * 12)(*iv)
+    _check(L.lib().fltee_gcm_finish_device(ids.ctypes.data_as(ctypes.c_void_p), n, _ptr(part), ct_bytes,
+                                           ivb, aad_len, _ptr(tags), _ptr(fail), _stream(stream)),
+           "fltee_gcm_finish_device")
+    return fail[:n]
+
+
+def decrypt_slice_auth(client_ids, window, row_stride, first_block, win_bytes, iv, records=None,
+                       stream=None):
+    """fltee_decrypt_slice_auth_device: the CTR half of GCM on one window of n slices ->
+    int64 [n, win_bytes // 8] records (nothing is verified here)."""
+    ids = np.ascontiguousarray(client_ids, dtype=np.uint32)
+    n = len(ids)
+    assert len(iv) == 12
+    if records is None:
+        records = torch.empty((n, win_bytes // 8), dtype=torch.int64, device=window.device)
+    ivb = (ctypes.c_uint8 * 12)(*iv)
+    _check(L.lib().fltee_decrypt_slice_auth_device(ids.ctypes.data_as(ctypes.c_void_p), n, _ptr(window),
+                                                   row_stride, first_block, win_bytes, ivb,
+                                                   _ptr(records), _stream(stream)),
+           "fltee_decrypt_slice_auth_device")
+    return records
+
+
 def laplace_r(d, k, n, seed, device="cuda", stream=None):
     r = torch.empty(d, dtype=torch.int32, device=device)
     T = ctypes.c_float(0)

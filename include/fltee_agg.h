@@ -292,6 +292,47 @@ fltee_status_t fltee_encrypt_auth_device(const uint32_t *client_ids, size_t n, c
 fltee_status_t fltee_debug_gcm_tag_host(uint32_t client_id, const uint8_t iv[12], const uint8_t *aad,
                                         size_t aad_len, const uint8_t *ct, size_t ct_len,
                                         uint8_t tag[16]);
+/* ---- the pieces of a COLUMN-SHARDED authenticated decrypt (device-resident, in the style of
+ * the fltee_*_range_device pieces): W workers each hold a window of every client's slice —
+ * the ciphertext blocks [first_block, first_block + ceil(win_bytes / 16)), n rows at
+ * row_stride bytes — and together verify and decrypt what fltee_decrypt_auth_device does on
+ * whole slices.  GHASH right-aligns a slice's AAD and ciphertext blocks in
+ * P = fltee_gcm_segments(ct_bytes, aad_len) segments of FLTEE_GCM_SEGMENT_BLOCKS blocks and
+ * keeps one 16-byte partial per segment; a partial is XOR-linear in its blocks, so
+ *   1. every worker: fltee_ghash_window_device -> its d_part (n x P x 16 bytes; segments its
+ *      window does not touch are zero); exactly one window of the slices passes with_aad = 1;
+ *   2. fltee_ghash_merge_device: d_acc ^= d_part, once per other worker;
+ *   3. fltee_gcm_finish_device on the merged partials and the n received tags (n x 16 bytes,
+ *      a buffer of their own: no worker's window has them behind it): d_fail[c] = 0 / 1 and
+ *      FLTEE_DEV_ERR_AUTH into the status word; the computed tags never leave the device;
+ *   4. every worker: fltee_decrypt_slice_auth_device, the CTR half alone on its window
+ *      (keystream block i of a row = E_K(IV || BE32(2 + first_block + i))) ->
+ *      n x floor(win_bytes / 8) records, compact.
+ * A partial is the field element as the kernels hold it: the 16 bytes of the GCM block, each
+ * byte with its bits reversed.  Refused with FLTEE_ERROR_INVALID_PARAMETER by host arithmetic,
+ * before any device call: aad_len > 64, ct_bytes > 2^36 - 32, a window that starts past the
+ * slice (16 first_block > ct_bytes), reaches past ct_bytes, or ends off a 16-byte boundary
+ * anywhere but at ct_bytes, and row_stride < win_bytes. */
+size_t fltee_gcm_segments(size_t ct_bytes, size_t aad_len);
+/* aad: n x aad_len bytes, read with with_aad != 0 only (aad_len shapes the layout either way) */
+fltee_status_t fltee_ghash_window_device(const uint32_t *client_ids, size_t n, const void *d_window,
+                                         size_t row_stride, size_t ct_bytes, size_t first_block,
+                                         size_t win_bytes, const uint8_t *aad, size_t aad_len,
+                                         int with_aad, void *d_part, void *stream);
+fltee_status_t fltee_ghash_merge_device(void *d_acc, const void *d_part, size_t n, size_t P,
+                                        void *stream);
+fltee_status_t fltee_gcm_finish_device(const uint32_t *client_ids, size_t n, const void *d_part,
+                                       size_t ct_bytes, const uint8_t iv[12], size_t aad_len,
+                                       const void *d_tags, uint32_t *d_fail, void *stream);
+fltee_status_t fltee_decrypt_slice_auth_device(const uint32_t *client_ids, size_t n,
+                                               const void *d_window, size_t row_stride,
+                                               size_t first_block, size_t win_bytes,
+                                               const uint8_t iv[12], void *d_records, void *stream);
+/* one client's window partials (P x 16 bytes) on the host by the same multiply (no GPU): for
+ * CPU tests; aad: this client's aad_len bytes; ct_window: the window's win_bytes bytes */
+fltee_status_t fltee_debug_ghash_window_host(uint32_t client_id, const uint8_t *aad, size_t aad_len,
+                                             int with_aad, const uint8_t *ct_window, size_t ct_bytes,
+                                             size_t first_block, size_t win_bytes, uint8_t *part_out);
 /* The ECALLs' upload format.  Off (default): plain AES-128-CTR with a zero counter block, as
  * lib.rs:312-343 and every earlier version of this library.  On: client c's slice is
  * ciphertext (B bytes) || tag (16 bytes) of the scheme above with
@@ -301,7 +342,13 @@ fltee_status_t fltee_debug_gcm_tag_host(uint32_t client_id, const uint8_t iv[12]
  * the records per client are floor(B / 8).  The existing refusals come first and stay 0x2;
  * a slice whose tag does not verify ends the call with *retval = FLTEE_ERROR_MAC_MISMATCH
  * before any aggregation is launched, [out] zero-filled, the round not advanced.  An eid over
- * several GPUs runs an authenticated ECALL on its root alone (the same bits). */
+ * several GPUs shards the authenticated ECALL as it shards the plain one, under the same
+ * contract and with the one-GPU bits: dense uploads by parameter range — every GPU copies,
+ * decrypts and hashes its own columns (the pieces above), the root XORs the partials, checks
+ * the tags and reads one verdict before any GPU sums; the position-range routes (algs 1, 2,
+ * 7) and alg 6's batches by whole clients — every GPU verifies the clients it loads, and the
+ * GPUs' verdicts are read before anything is sorted or folded.  A shape the group declines
+ * runs authenticated on the root. */
 void fltee_set_upload_aead(int on);
 
 /* out[j] = coef * sum_r rows[r*d + j], rows added in order (exact fp32): the
