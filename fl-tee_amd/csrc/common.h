@@ -454,6 +454,13 @@ hipError_t launch_ghash_finish_tags(uint8_t *tags, size_t tag_stride, size_t n, 
 void ghash_window_host(const uint8_t h[16], const uint8_t *aad, size_t aad_len, bool with_aad,
                        const uint8_t *ct_window, size_t ct_bytes, uint64_t first_block,
                        size_t win_bytes, uint8_t *part_out);
+// k_survivors.hip: out[s][0..k) = rec[keep[s]][0..k), s < n_keep (n x k records of 8 bytes,
+// a shape gather_clients_fits accepts; keep in device memory; out never overlaps rec).  A
+// keep[s] >= n is clamped and ORs FLTEE_DEV_ERR_LAUNCH into *status.
+bool gather_clients_fits(size_t n, size_t k, size_t n_keep);
+hipError_t launch_gather_clients(const void *rec, size_t n, size_t k, const uint32_t *keep,
+                                 size_t n_keep, void *out, uint32_t *status, hipStream_t s);
+
 void gf128_mul_host(const uint8_t a[16], const uint8_t b[16], uint8_t out[16]);
 void gcm_tag_host(const uint8_t h[16], const uint8_t ej0[16], const uint8_t *aad, size_t aad_len,
                   const uint8_t *ct, size_t ct_len, uint8_t tag[16]);

@@ -125,6 +125,30 @@ constexpr size_t kLoadChunkBytes = (size_t)64 << 20;
 
 // ---- authenticated uploads (fltee_set_upload_aead; k_ghash.hip) ----------------------
 static bool g_upload_aead = false;
+// What follows a failed tag (fltee_set_upload_aead_policy): ABORT, REPORT or DROP, and DROP's
+// quorum (>= 1)
+static int g_aead_policy = FLTEE_AEAD_ABORT;
+static size_t g_aead_min_survivors = 1;
+
+// The verdict of fl_id's last authenticated ECALL under REPORT / DROP (fltee_auth_report):
+// the failed client ids in upload order; empty after a clean call
+struct AuthReport {
+    uint32_t round = 0;
+    std::vector<uint32_t> failed;
+};
+static std::map<uint32_t, AuthReport> g_auth_reports;
+
+static bool keeps_verdict(bool aead) { return aead && g_aead_policy != FLTEE_AEAD_ABORT; }
+
+// fail: the n fail words as load_and_decrypt read them back (the word gathering them behind)
+static void store_auth_report(uint32_t fl_id, uint32_t round, const uint32_t *ids, size_t n,
+                              const std::vector<uint32_t> &fail) {
+    AuthReport &r = g_auth_reports[fl_id];
+    r.round = round;
+    r.failed.clear();
+    for (size_t i = 0; i < n; ++i)
+        if (fail[i]) r.failed.push_back(ids[i]);
+}
 
 // One call's GCM parameters: the IV, and aad_len bytes of AAD per client.
 struct GcmArgs {
@@ -228,9 +252,12 @@ static uint32_t gcm_verify(const GcmDev &d, size_t c0, size_t nc, const uint8_t 
 
 // g (fltee_set_upload_aead): bpc is the slice stride B + 16; every chunk is authenticated
 // next to its decryption, and the word gathering FLTEE_DEV_ERR_AUTH is read at the
-// synchronisation that ends the decryption: FLTEE_ERROR_MAC_MISMATCH.
+// synchronisation that ends the decryption: FLTEE_ERROR_MAC_MISMATCH.  verdict (with g; the
+// REPORT / DROP policies): that one readback also takes the n fail words in front of the
+// word — (n + 1) * 4 bytes, a function of n alone — into verdict[0 .. n].
 static uint32_t load_and_decrypt(DeviceCtx *c, const uint32_t *ids, size_t n, const uint8_t *enc,
-                                 size_t bpc, float *t_load, float *t_dec, const GcmArgs *g = nullptr) {
+                                 size_t bpc, float *t_load, float *t_dec, const GcmArgs *g = nullptr,
+                                 std::vector<uint32_t> *verdict = nullptr) {
     const size_t ctb = g ? bpc - FLTEE_GCM_TAG_BYTES : bpc;
     const size_t rpc = ctb / 8;
     const double t0 = now_s();
@@ -277,11 +304,17 @@ static uint32_t load_and_decrypt(DeviceCtx *c, const uint32_t *ids, size_t n, co
     if (fl_stream_sync(c->copy_stream) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
     const double t1 = now_s();
     if (t_load) *t_load = (float)(t1 - t0);
-    if (g && fl_memcpy_async(&auth, gd.auth_word, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+    if (g && verdict) {
+        verdict->assign(n + 1, 0);
+        if (fl_memcpy_async(verdict->data(), gd.fail, (n + 1) * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            return FLTEE_ERROR_UNEXPECTED;
+    } else if (g && fl_memcpy_async(&auth, gd.auth_word, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
         return FLTEE_ERROR_UNEXPECTED;
+    }
     // rk lives on this stack frame: the decrypt (and the key upload) must finish here
     if (fl_stream_sync(c->stream) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
     if (t_dec) *t_dec = (float)(now_s() - t1);
+    if (g && verdict) auth = (*verdict)[n];
     return auth ? FLTEE_ERROR_MAC_MISMATCH : FLTEE_SUCCESS;
 }
 
@@ -349,13 +382,16 @@ static uint32_t status_to_retval(uint32_t dev_st, uint32_t alg, bool *retry) {
 
 // Aggregate c->records (n clients x rpc records) with alg into the device out buffer,
 // reading the status word back (one sync) and rerunning only where status_to_retval says.
+// rec: the records when they are not c->records (the survivors of a DROP call).
 static uint32_t aggregate_records(DeviceCtx *c, uint32_t alg, size_t n, size_t rpc, size_t d,
-                                  size_t k_req, size_t batch, float *d_out, uint64_t seed = 0) {
+                                  size_t k_req, size_t batch, float *d_out, uint64_t seed = 0,
+                                  const void *rec = nullptr) {
     fltee_device_opts o = ecall_opts(alg, n, rpc, d, k_req, batch, seed);
     if (alg == FLTEE_ALG_OPTIMIZED) o.flags &= ~FLTEE_OPT_K_REQ;
+    if (!rec) rec = c->records.ptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (fl_memset_async(c->status, 0, 4, c->stream) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
-        uint32_t st = aggregate(alg, c->records.ptr, n, rpc, d, d_out, o, c->stream, c->status);
+        uint32_t st = aggregate(alg, rec, n, rpc, d, d_out, o, c->stream, c->status);
         if (st != FLTEE_SUCCESS) return st;
         uint32_t dev_st = 0;
         if (read_status(c, &dev_st)) return FLTEE_ERROR_UNEXPECTED;
@@ -365,6 +401,35 @@ static uint32_t aggregate_records(DeviceCtx *c, uint32_t alg, size_t n, size_t r
         o.flags &= ~FLTEE_OPT_DENSE;  // the sparse path: exact for any upload
     }
     return FLTEE_ERROR_INVALID_PARAMETER;
+}
+
+// FLTEE_AEAD_DROP after a failing verdict (fail[0 .. n) from load_and_decrypt): S = the
+// verified clients in upload order, n' = |S|.  Below the quorum the call ends as under ABORT
+// (FLTEE_ERROR_MAC_MISMATCH).  Otherwise c->records (n x rpc) is compacted into c->survivors
+// (k_survivors.hip; reserved here, on the failure path only) and *rec / *n_keep say what to
+// aggregate.  The keep list goes up asynchronously on the call's stream, from c->keep_host;
+// nothing here synchronises.  Launch shapes: the public sizes and the failed set.  (The
+// indices are the host's own, all < n: the kernel's range flag cannot be raised here.)
+static uint32_t gather_survivors(DeviceCtx *c, const std::vector<uint32_t> &fail, size_t n, size_t rpc,
+                                 size_t *n_keep, const void **rec) {
+    std::vector<uint32_t> &keep = c->keep_host;
+    keep.clear();
+    for (size_t i = 0; i < n; ++i)
+        if (!fail[i]) keep.push_back((uint32_t)i);
+    const size_t ns = keep.size();
+    if (ns < g_aead_min_survivors || ns == 0) return FLTEE_ERROR_MAC_MISMATCH;
+    *n_keep = ns;
+    if (ns == n) return FLTEE_SUCCESS;
+    if (!gather_clients_fits(n, rpc, ns)) return FLTEE_ERROR_MAC_MISMATCH;  // past the gather's grid
+    const size_t recb = (ns * rpc * 8 + 15) / 16 * 16;
+    if (!c->survivors.reserve(recb + ns * 4)) return FLTEE_ERROR_OUT_OF_MEMORY;
+    uint32_t *d_keep = (uint32_t *)((uint8_t *)c->survivors.ptr + recb);
+    if (fl_memcpy_async(d_keep, keep.data(), ns * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        launch_gather_clients(c->records.ptr, n, rpc, d_keep, ns, c->survivors.ptr, c->status,
+                              c->stream) != hipSuccess)
+        return FLTEE_ERROR_UNEXPECTED;
+    *rec = c->survivors.ptr;
+    return FLTEE_SUCCESS;
 }
 
 // Small calls (payload <= kStagedBytes) on one GPU with ONE host synchronisation. The
@@ -563,6 +628,7 @@ extern "C" fltee_status_t ecall_fl_init(fltee_eid_t eid, fltee_status_t *retval,
     for (size_t i = 0; i < client_size; ++i) g_keys.insert(client_ids[i]);  // lib.rs:163-174
     g_have_keys = true;
     g_cfg[fl_id] = std::move(cfg);
+    g_auth_reports.erase(fl_id);  // a verdict belongs to the config it was read under
     if (verbose) std::printf("[FLTEE] make fl config id %u\n", fl_id);
     *retval = FLTEE_SUCCESS;
     return FLTEE_SUCCESS;
@@ -668,6 +734,12 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     const size_t tagb = aead ? FLTEE_GCM_TAG_BYTES : 0;
     uint32_t st = FLTEE_GROUP_FALLBACK;
     double t2 = 0;
+    // REPORT / DROP: the per-client verdict is kept.  A group path that read a failing verdict
+    // stopped before any aggregation launch, as under ABORT; the call then continues on the
+    // root alone (below), which loads and verifies the whole payload again for the fail words
+    const bool keepv = keeps_verdict(aead);
+    bool verdict_stored = false;
+    bool group_tried = false;  // a shape the group declined (or failed on) is not offered to it again
     const bool flat = aggregation_alg == FLTEE_ALG_BASELINE || aggregation_alg == FLTEE_ALG_PATH_ORAM ||
                       aggregation_alg == FLTEE_ALG_NON_OBLIVIOUS;
     const bool tree = ecall_takes_tree(aggregation_alg, n, rpc, d);
@@ -684,6 +756,10 @@ extern "C" fltee_status_t ecall_secure_aggregation(
                                false,  // out of position: the root's sparse rerun, every alg
                                aead ? &gh : nullptr);
         t2 = now_s();
+        if (st == FLTEE_ERROR_MAC_MISMATCH && keepv) {
+            st = FLTEE_GROUP_FALLBACK;
+            group_tried = true;
+        }
         if (st != FLTEE_SUCCESS && st != FLTEE_GROUP_FALLBACK) return fail(st);
     }
     // (the exact-runs policy folds on one GPU: one sequential walk of the sorted array)
@@ -695,8 +771,7 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     // nips19 draws its seed (Laplace counts, shuffle key) once per call, whichever path
     // runs it, so a multi-GPU eid consumes the seed sequence exactly as one GPU does
     const uint64_t seed = aggregation_alg == FLTEE_ALG_NIPS19 ? next_seed() : 0;
-    bool group_tried = false;  // a shape the group declined is not offered to it again
-    if (st == FLTEE_GROUP_FALLBACK && sharded && group_splits_host_copy(G)) {
+    if (st == FLTEE_GROUP_FALLBACK && sharded && !group_tried && group_splits_host_copy(G)) {
         // every GPU copies and decrypts (authenticated: and verifies) the clients of its own
         // position range
         std::vector<uint32_t> rk;
@@ -716,6 +791,7 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         else
             st = group_nips19(G, c, in, n, rpc, k_req, d, seed, coef, d_out);
         group_tried = true;
+        if (st == FLTEE_ERROR_MAC_MISMATCH && keepv) st = FLTEE_GROUP_FALLBACK;
         if (st != FLTEE_SUCCESS && st != FLTEE_GROUP_FALLBACK) return fail(st);
         // "Aggregation" = the call minus its load and decrypt phases
         t2 = ta + execution_time_results[0] + execution_time_results[1];
@@ -737,16 +813,25 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         *retval = FLTEE_SUCCESS;
         return FLTEE_SUCCESS;
     }
+    size_t n_agg = n;  // DROP: n', the verified clients; everything that depends on n takes it
     if (st == FLTEE_GROUP_FALLBACK) {  // (a shape the per-GPU path declines comes here too)
+        if (G && hipSetDevice(c->device) != hipSuccess) return fail(FLTEE_ERROR_UNEXPECTED);
+        std::vector<uint32_t> verdict;
         st = load_and_decrypt(c, client_ids, n, encrypted_parameters_data, bpc,
                               &execution_time_results[0], &execution_time_results[1],
-                              aead ? &gcm : nullptr);
+                              aead ? &gcm : nullptr, keepv ? &verdict : nullptr);
+        const void *rec = nullptr;
+        if (keepv && (st == FLTEE_SUCCESS || st == FLTEE_ERROR_MAC_MISMATCH)) {
+            store_auth_report(fl_id, round, client_ids, n, verdict);
+            verdict_stored = true;
+            if (st && g_aead_policy == FLTEE_AEAD_DROP) st = gather_survivors(c, verdict, n, rpc, &n_agg, &rec);
+        }
         if (st) return fail(st);  // (a tag mismatch: the timers stay written)
         t2 = now_s();
         st = FLTEE_GROUP_FALLBACK;
         GroupInput in;
         in.root_rec = (const uint64_t *)c->records.ptr;
-        if (sharded && !group_tried) {
+        if (sharded && !group_tried && n_agg == n) {
             if (aggregation_alg == FLTEE_ALG_ADVANCED)
                 st = group_advanced(G, in, n, rpc, d, coef, d_out);
             else if (aggregation_alg == FLTEE_ALG_BUBBLE)
@@ -755,10 +840,10 @@ extern "C" fltee_status_t ecall_secure_aggregation(
                 st = group_nips19(G, c, in, n, rpc, k_req, d, seed, coef, d_out);
         }
         if (st == FLTEE_GROUP_FALLBACK)  // one device (or a shape the group does not shard)
-            st = aggregate_records(c, aggregation_alg, n, rpc, d, k_req, 0, d_out, seed);
+            st = aggregate_records(c, aggregation_alg, n_agg, rpc, d, k_req, 0, d_out, seed, rec);
     }
     if (!st && cfg.dp) {  // lib.rs:399-408
-        if (launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n, next_seed(), c->stream) != hipSuccess)
+        if (launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n_agg, next_seed(), c->stream) != hipSuccess)
             st = FLTEE_ERROR_UNEXPECTED;
     }
     if (!st && fl_memcpy_async(updated_parameters_data, d_out, d * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
@@ -768,6 +853,8 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         std::memset(updated_parameters_data, 0, d * sizeof(float));
         return fail(st);
     }
+    // (a group path answered the call: every rank's verdict was clean)
+    if (keepv && !verdict_stored) store_auth_report(fl_id, round, client_ids, 0, {});
     execution_time_results[2] = (float)(now_s() - t2);
     if (cfg.verbose)
         std::printf("[FLTEE CLOCK] Loading %.6f Decryption %.6f Aggregation %.6f seconds\n",
@@ -815,8 +902,15 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
     float *d_out = nullptr;
     if (!c->outbuf.reserve(d * 4 + 16)) return fail(FLTEE_ERROR_OUT_OF_MEMORY);
     d_out = (float *)c->outbuf.ptr;
-    uint32_t st;
+    uint32_t st = FLTEE_SUCCESS;
     Group *G = group_of(eid);
+    // REPORT / DROP keep the per-client verdict: a group that read a failing one stopped before
+    // any batch was launched, and the call continues on the root alone, which loads and
+    // verifies the whole payload again for the fail words
+    const bool keepv = keeps_verdict(aead);
+    bool verdict_stored = false;
+    bool on_root = true;  // load, verify and aggregate through the root's context
+    size_t n_agg = n;     // DROP: n', the verified clients
     if (G && group_splits_host_copy(G)) {
         // the batches split over the eid's GPUs, each loading (authenticated: and verifying)
         // its own clients (group.hip)
@@ -843,6 +937,7 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
         st = group_optimized(G, in, n, k, d, optimal_num_of_clients, 1.0f / (float)n, d_out, halo6);
         execution_time_results[0] = t_load;
         if (st == FLTEE_ERROR_MAC_MISMATCH) execution_time_results[1] = t_dec;
+        on_root = st == FLTEE_ERROR_MAC_MISMATCH && keepv;
     } else if (!G && !aead && n * k * 8 <= kStagedBytes) {
         // one GPU, a small payload: one DMA each way, one host synchronisation
         st = staged_ecall(c, FLTEE_ALG_OPTIMIZED, client_ids, n, encrypted_parameters_data_ptr, k * 8, d,
@@ -855,22 +950,32 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
         cfg.round += 1;
         *retval = FLTEE_SUCCESS;
         return FLTEE_SUCCESS;
-    } else {
+    }
+    if (on_root) {
+        const bool group_failed = st == FLTEE_ERROR_MAC_MISMATCH;
+        if (G && hipSetDevice(c->device) != hipSuccess) return fail(FLTEE_ERROR_UNEXPECTED);
+        std::vector<uint32_t> verdict;
         st = load_and_decrypt(c, client_ids, n, encrypted_parameters_data_ptr, bpc6, &t_load, &t_dec,
-                              aead ? &gcm : nullptr);
+                              aead ? &gcm : nullptr, keepv ? &verdict : nullptr);
         execution_time_results[0] = t_load;
         if (st == FLTEE_ERROR_MAC_MISMATCH) execution_time_results[1] = t_dec;
+        const void *rec = nullptr;
+        if (keepv && (st == FLTEE_SUCCESS || st == FLTEE_ERROR_MAC_MISMATCH)) {
+            store_auth_report(fl_id, round, client_ids, n, verdict);
+            verdict_stored = true;
+            if (st && g_aead_policy == FLTEE_AEAD_DROP) st = gather_survivors(c, verdict, n, k, &n_agg, &rec);
+        }
         if (st) return fail(st);
-        if (G) {
+        if (G && !group_failed && n_agg == n) {
             GroupInput in;
             in.root_rec = (const uint64_t *)c->records.ptr;
             st = group_optimized(G, in, n, k, d, optimal_num_of_clients, 1.0f / (float)n, d_out, halo6);
         } else {
-            st = aggregate_records(c, FLTEE_ALG_OPTIMIZED, n, k, d, k, optimal_num_of_clients, d_out);
+            st = aggregate_records(c, FLTEE_ALG_OPTIMIZED, n_agg, k, d, k, optimal_num_of_clients, d_out, 0, rec);
         }
     }
     if (!st && cfg.dp) {  // lib.rs:586-588
-        if (launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n, next_seed(), c->stream) != hipSuccess)
+        if (launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n_agg, next_seed(), c->stream) != hipSuccess)
             st = FLTEE_ERROR_UNEXPECTED;
     }
     if (!st && fl_memcpy_async(updated_parameters_data, d_out, d * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
@@ -880,6 +985,7 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
         std::memset(updated_parameters_data, 0, d * sizeof(float));
         return fail(st);
     }
+    if (keepv && !verdict_stored) store_auth_report(fl_id, round, client_ids, 0, {});  // (a clean group call)
     execution_time_results[1] = (float)(now_s() - t1) - t_load;  // decrypt + aggregate
     cfg.round += 1;
     *retval = FLTEE_SUCCESS;
@@ -1101,6 +1207,49 @@ extern "C" fltee_status_t fltee_debug_ghash_window_host(uint32_t client_id, cons
 extern "C" void fltee_set_upload_aead(int on) {
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
     g_upload_aead = on != 0;
+}
+
+extern "C" void fltee_set_upload_aead_policy(int policy, size_t min_survivors) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    // (an unknown value is the default: a host never gets a weaker contract by mistake)
+    g_aead_policy = policy == FLTEE_AEAD_REPORT || policy == FLTEE_AEAD_DROP ? policy : FLTEE_AEAD_ABORT;
+    g_aead_min_survivors = min_survivors ? min_survivors : 1;
+}
+
+extern "C" fltee_status_t fltee_auth_report(fltee_eid_t eid, uint32_t fl_id, uint32_t *round,
+                                            uint32_t *failed_ids, size_t cap, size_t *n_failed) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    if (!n_failed || (cap && !failed_ids)) return FLTEE_ERROR_INVALID_PARAMETER;
+    *n_failed = 0;
+    // the configs (and so the verdicts) are keyed by fl_id for the whole process, like
+    // FL_CONFIG_MAP: an unknown fl_id is answered first, whatever the eid
+    auto cf = g_cfg.find(fl_id);
+    if (cf == g_cfg.end()) return FLTEE_ERROR_UNEXPECTED;
+    if (eid == 0 || eid > g_eid_dev.size() || g_eid_dev[eid - 1] < 0) return FLTEE_ERROR_INVALID_ENCLAVE_ID;
+    auto it = g_auth_reports.find(fl_id);
+    if (it == g_auth_reports.end()) {  // no verdict stored (ABORT, AEAD off, no call yet)
+        if (round) *round = cf->second.round;
+        return FLTEE_SUCCESS;
+    }
+    const AuthReport &r = it->second;
+    if (round) *round = r.round;
+    *n_failed = r.failed.size();
+    std::copy(r.failed.begin(), r.failed.begin() + std::min(cap, r.failed.size()), failed_ids);
+    return FLTEE_SUCCESS;
+}
+
+extern "C" fltee_status_t fltee_gather_clients_device(const void *d_records, size_t n, size_t k,
+                                                      const uint32_t *d_keep, size_t n_keep,
+                                                      void *d_out, void *stream) {
+    if (!d_records || !d_keep || !d_out || n_keep > n || k == 0 || n > (((size_t)1 << 31) - 1) / k)
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    if (n_keep == 0) return FLTEE_SUCCESS;
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    DeviceCtx *c = current_ctx();
+    if (!c) return FLTEE_ERROR_INVALID_PARAMETER;
+    return launch_gather_clients(d_records, n, k, d_keep, n_keep, d_out, c->status,
+                                 (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
 }
 
 // CPU self-test hooks: the one GF(2^128) multiply (GCM byte order), the subkeys H ||

@@ -1,6 +1,7 @@
 // engine.h — per-device state and the internal aggregation entry points.
 #pragma once
 #include <mutex>
+#include <vector>
 
 #include "common.h"
 
@@ -97,6 +98,11 @@ struct DeviceCtx {
     hipEvent_t call_ev[3] = {};                          // small ECALLs: the phase timers
     // authenticated uploads (k_ghash.hip): subkeys + AAD, powers of H, partials, fail words
     Buffer gcm_sub, gcm_pow, gcm_part, gcm_fail;
+    // FLTEE_AEAD_DROP: the verified clients' records, compacted (k_survivors.hip), their
+    // keep list behind them; reserved only by a call that drops a client.  keep_host: the
+    // list's host side, alive until the next call (its upload is asynchronous)
+    Buffer survivors;
+    std::vector<uint32_t> keep_host;
     Buffer ws_client, ws_client_coef;                   // client-side producers
     Buffer ws_cnt, ws_sel;                               // nips19's selected list
     Buffer ws_keys, ws_radix;  // ordered folds: records sorted by idx, the counting sort's scratch

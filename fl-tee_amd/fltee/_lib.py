@@ -35,6 +35,8 @@ DEV_ERR_AUTH = 0x10
 GCM_SEGMENT_BLOCKS = 512  # FLTEE_GCM_SEGMENT_BLOCKS: 16-byte blocks per GHASH segment
 GCM_TAG_BYTES = 16
 GCM_MAX_AAD = 64
+# fltee_set_upload_aead_policy: what an authenticated ECALL does after a failed tag
+AEAD_ABORT, AEAD_REPORT, AEAD_DROP = 0, 1, 2
 
 OPT_DENSE = 0x1
 OPT_DP = 0x2
@@ -86,6 +88,9 @@ SIGNATURES = {
     "fltee_decrypt_slice_auth_device": (_U32, [_P, _S, _P, _S, _S, _S, _P, _P, _P]),
     "fltee_debug_ghash_window_host": (_U32, [_U32, _P, _S, ctypes.c_int, _P, _S, _S, _S, _P]),
     "fltee_set_upload_aead": (None, [ctypes.c_int]),
+    "fltee_set_upload_aead_policy": (None, [ctypes.c_int, _S]),
+    "fltee_auth_report": (_U32, [_U64, _U32, _P, _P, _S, _P]),
+    "fltee_gather_clients_device": (_U32, [_P, _S, _S, _P, _S, _P, _P]),
     "fltee_device_status": (_U32, [_P, _P]),
     "fltee_sum_rows_device": (_U32, [_P, _S, _S, _F, _P, _P]),
     "fltee_dp_noise_device": (_U32, [_P, _S, _F, _F, _S, _U64, _P]),

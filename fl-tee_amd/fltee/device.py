@@ -136,6 +136,28 @@ def decrypt_auth(client_ids, cipher, ct_bytes, iv, aad=b"", records=None, stream
     return records[:n * (ct_bytes // 8)], fail[:n]
 
 
+def gather_clients(records, keep, out=None, stream=None):
+    """fltee_gather_clients_device: the slices keep[0], keep[1], ... (ascending client
+    positions) of records, an (n, k) int64 cuda tensor of client-major records, compacted into
+    out (len(keep), k) — a second buffer, never records itself.  keep: a cuda int32 tensor, or
+    host integers (uploaded here)."""
+    assert records.is_cuda and records.dtype == torch.int64 and records.dim() == 2
+    n, k = records.shape
+    assert records.stride(1) == 1 and records.stride(0) == k, "client-major, slices back to back"
+    if not torch.is_tensor(keep):
+        keep = torch.from_numpy(np.ascontiguousarray(keep, dtype=np.int32))
+    keep = keep.to(device=records.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty((keep.numel(), k), dtype=torch.int64, device=records.device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= keep.numel() * k
+    # an empty tensor may have a null data pointer: the library refuses those before it looks at n_keep
+    anchor = records if keep.numel() == 0 else keep
+    _check(L.lib().fltee_gather_clients_device(_ptr(records), n, k, _ptr(anchor), keep.numel(),
+                                               _ptr(out if out.numel() else records), _stream(stream)),
+           "fltee_gather_clients_device")
+    return out
+
+
 def gcm_segments(ct_bytes, aad_len):
     """fltee_gcm_segments: GHASH partials per client of a slice of ct_bytes with aad_len of AAD."""
     return L.lib().fltee_gcm_segments(ct_bytes, aad_len)

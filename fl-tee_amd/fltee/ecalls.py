@@ -104,6 +104,20 @@ class Enclave:
             _p(times))
         return st, rv.value, out, times
 
+    def auth_report(self, fl_id):
+        """fltee_auth_report: (round, [failed client ids in upload order]) of fl_id's last
+        authenticated ECALL under the "report" / "drop" policies; an empty list after a clean
+        call, and when nothing was stored."""
+        rnd, n = ctypes.c_uint32(0), ctypes.c_size_t(0)
+        st = self.lib.fltee_auth_report(self.eid, fl_id, ctypes.byref(rnd), None, 0, ctypes.byref(n))
+        ids = np.zeros(max(n.value, 1), dtype=np.uint32)
+        if st == L.SUCCESS and n.value:
+            st = self.lib.fltee_auth_report(self.eid, fl_id, ctypes.byref(rnd), _p(ids), n.value,
+                                            ctypes.byref(n))
+        if st != L.SUCCESS:
+            raise RuntimeError(f"fltee_auth_report({fl_id}) failed: {st:#x}")
+        return rnd.value, [int(x) for x in ids[:n.value]]
+
 
 def set_debug_seed(seed):
     """Deterministic RNG for sampling / nips19 / DP (tests only; 0 restores RDRAND-like)."""
@@ -128,6 +142,21 @@ def set_upload_aead(on):
     global _upload_aead
     L.lib().fltee_set_upload_aead(1 if on else 0)
     _upload_aead = bool(on)
+
+
+AEAD_POLICIES = {"abort": L.AEAD_ABORT, "report": L.AEAD_REPORT, "drop": L.AEAD_DROP}
+
+
+def set_upload_aead_policy(policy, min_survivors=1):
+    """What an authenticated ECALL does after a failed tag (fltee_set_upload_aead_policy;
+    no effect while AEAD is off).  policy: "abort" (default: 0x3001, nothing more), "report"
+    (0x3001, and Enclave.auth_report names the failed clients) or "drop" (the verified
+    clients are aggregated, with n' in every divisor, when at least min_survivors verified;
+    else as "report"), or the FLTEE_AEAD_* value."""
+    code = AEAD_POLICIES[policy] if isinstance(policy, str) else int(policy)
+    if code not in AEAD_POLICIES.values():
+        raise ValueError(f"unknown AEAD policy {policy!r}")
+    L.lib().fltee_set_upload_aead_policy(code, int(min_survivors))
 
 
 def set_bubble_ecall(on):

@@ -8,6 +8,7 @@ code); the handlers are fltee.server.Aggregator, the server.rs logic over the C 
 
     python -m fltee.grpc_server [--address 0.0.0.0:50051] [--device 0] [--dp]
                                 [--strict-reference] [--quiet]
+                                [--aead [--aead-policy abort|report|drop]]
 
 Like the reference: verbose on, dp off (server.rs:236-237; --dp turns DP on for
 the configs[3] runs), one enclave per process; calls are serialised by the
@@ -116,10 +117,18 @@ def main(argv=None):
                     help="apply server.rs:126-128's optimal_num_of_clients check to every alg")
     ap.add_argument("--aead", action="store_true",
                     help="authenticated uploads: AES-128-GCM, ciphertext || 16-byte tag per client")
+    ap.add_argument("--aead-policy", choices=("abort", "report", "drop"), default=None,
+                    help="with --aead, after a failed tag: abort the round (default), abort and "
+                         "log the failed clients, or aggregate the verified clients")
+    ap.add_argument("--aead-min-survivors", type=int, default=1,
+                    help="--aead-policy drop: verified clients needed to answer the round")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
+    if args.aead_policy is not None and not args.aead:
+        ap.error("--aead-policy needs --aead")
     agg = Aggregator(device=args.device, verbose=not args.quiet, dp=args.dp,
-                     strict_reference=args.strict_reference, aead=args.aead)
+                     strict_reference=args.strict_reference, aead=args.aead,
+                     aead_policy=args.aead_policy or "abort", min_survivors=args.aead_min_survivors)
     server, port = make_server(agg, args.address, verbose=not args.quiet)
     server.start()
     print(f"[Server] Now GRPC Server is binded on {args.address} (port {port})", flush=True)

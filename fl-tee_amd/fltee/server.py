@@ -14,11 +14,16 @@ request).  Documented deviations from the reference host:
   * `aead=True` (off by default) switches the uploads to AES-128-GCM: the request's
     encrypted_parameters then carries ciphertext || 16-byte tag per client (the proto is
     unchanged), and a slice that does not verify is a ServerPanic naming the MAC mismatch.
+  * `aead_policy` (with `aead=True`): "abort" (default) as above; "report": the same panic,
+    and the clients whose slices failed are kept in `last_failed_clients` and logged;
+    "drop": the verified clients are aggregated (the averages take their count) as long as
+    `min_survivors` of them verified, the failed ones kept and logged the same way.  The
+    reply has no field for the list (the proto is unchanged): the host reads it here.
 """
 import time
 
 from . import _lib as L
-from .ecalls import Enclave, set_upload_aead
+from .ecalls import AEAD_POLICIES, Enclave, set_upload_aead, set_upload_aead_policy
 
 
 class ServerPanic(RuntimeError):
@@ -27,11 +32,18 @@ class ServerPanic(RuntimeError):
 
 class Aggregator:
     def __init__(self, device=0, verbose=False, dp=False, strict_reference=False, enclave=None,
-                 aead=False):
+                 aead=False, aead_policy="abort", min_survivors=1):
+        if aead_policy not in AEAD_POLICIES:
+            raise ValueError(f"aead_policy must be one of {sorted(AEAD_POLICIES)}")
+        if aead_policy != "abort" and not aead:
+            raise ValueError("aead_policy needs aead=True")
         self.enclave = enclave if enclave is not None else Enclave(device)
         self.aead = bool(aead)
+        self.aead_policy = aead_policy
+        self.last_failed_clients = []  # of the last aggregate, under "report" / "drop"
         if self.aead:  # process-wide, like the enclave's other start-up switches
             set_upload_aead(True)
+            set_upload_aead_policy(aead_policy, min_survivors)
         self.verbose = verbose
         self.dp = dp
         self.strict_reference = strict_reference
@@ -51,16 +63,31 @@ class Aggregator:
             raise ServerPanic("Error at ecall_start_round")
         return dict(fl_id=fl_id, round=0, client_ids=[int(x) for x in sampled])
 
+    def _note_failed_clients(self, fl_id, round, st, rv):
+        """under "report" / "drop", after an ECALL that reached its verdict (answered, or a
+        MAC mismatch): keep and log the clients whose slices did not verify"""
+        if not self.aead or self.aead_policy == "abort" or st != L.SUCCESS:
+            return
+        if rv not in (L.SUCCESS, L.ERROR_MAC_MISMATCH):
+            return
+        rnd, failed = self.enclave.auth_report(fl_id)
+        if rnd == round and failed:
+            self.last_failed_clients = failed
+            print(f"[Server] fl_id={fl_id} round={round}: {len(failed)} client(s) failed "
+                  f"authentication: {failed}", flush=True)
+
     # server.rs:111-215
     def aggregate(self, fl_id, round, encrypted_parameters, num_of_parameters,
                   num_of_sparse_parameters, optimal_num_of_clients, aggregation_alg, client_ids):
         if optimal_num_of_clients > len(client_ids) and (self.strict_reference or aggregation_alg == 6):
             raise ServerPanic(f"optimal_num_of_clients is more than client size {len(client_ids)}")
         t0 = time.perf_counter()
+        self.last_failed_clients = []
         if aggregation_alg == 6:
             st, rv, out, times = self.enclave.ecall_client_size_optimized_secure_aggregation(
                 fl_id, round, optimal_num_of_clients, client_ids, encrypted_parameters,
                 num_of_parameters, num_of_sparse_parameters, aggregation_alg)
+            self._note_failed_clients(fl_id, round, st, rv)
             if st == L.SUCCESS and rv == L.ERROR_MAC_MISMATCH:
                 raise ServerPanic("MAC mismatch at ecall_client_size_optimized_secure_aggregation")
             if st != L.SUCCESS or rv != L.SUCCESS:
@@ -69,6 +96,7 @@ class Aggregator:
             st, rv, out, times = self.enclave.ecall_secure_aggregation(
                 fl_id, round, client_ids, encrypted_parameters, num_of_parameters,
                 num_of_sparse_parameters, aggregation_alg)
+            self._note_failed_clients(fl_id, round, st, rv)
             if st == L.SUCCESS and rv == L.ERROR_MAC_MISMATCH:
                 raise ServerPanic("MAC mismatch at ecall_secure_aggregation")
             if st != L.SUCCESS or rv != L.SUCCESS:

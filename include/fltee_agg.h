@@ -351,6 +351,58 @@ fltee_status_t fltee_debug_ghash_window_host(uint32_t client_id, const uint8_t *
  * runs authenticated on the root. */
 void fltee_set_upload_aead(int on);
 
+/* What an authenticated ECALL does after its verdict (process-wide, like fltee_set_upload_aead;
+ * no effect while AEAD is off).  The device holds one fail word per client.
+ *   ABORT  (default): as above, and as every earlier version: only the OR of the fail words is
+ *          read; a failure ends the call with 0x3001 and the host learns nothing more.
+ *   REPORT: the call ends as under ABORT, but the one readback of the verdict also takes the n
+ *          fail words ((n + 1) * 4 bytes, a function of n alone, at the same place and the same
+ *          synchronisation), and fltee_auth_report names the clients that failed.
+ *   DROP:  the verdict is kept, and the call aggregates the verified clients.  With S = the
+ *          verified clients in upload order and n' = |S| >= max(1, min_survivors): *retval = 0,
+ *          the timers are written, the round advances, and [out] is bit for bit what the same
+ *          ECALL on the same kind of eid returns for the clients of S alone (their ids, their
+ *          slices in order, client_size = n'): the 1/n' average, the DP noise divisor, nips19's
+ *          threshold and alg 6's batches (re-formed over S in order) all take n'; nips19 and DP
+ *          draw their seeds once per call.  With fewer survivors the call ends as under REPORT.
+ *          The 0x2 refusals come first and are evaluated on the request as sent.  A clean call
+ *          runs the launches it runs under ABORT.  After a failing verdict the records of S are
+ *          compacted into a second buffer (fltee_gather_clients_device's kernel; its scratch is
+ *          reserved on this path only) and the launch shapes depend on the public sizes and on
+ *          the failed set — which the host can cause, and reads from the report.  On an eid
+ *          over several GPUs a group path that read a failing verdict stops before any
+ *          aggregation launch, as under ABORT; under REPORT and DROP the root alone then loads
+ *          and verifies the whole payload again (for the per-client words) and, under DROP,
+ *          aggregates the survivors: the one-GPU bits, the second load paid only by a call with
+ *          a failure.  A payload past one gather launch (n or k above 2^32 - 1, or more than
+ *          2^31 - 1 blocks of 2048 records) is not dropped from: such a call ends as under
+ *          REPORT. */
+#define FLTEE_AEAD_ABORT 0
+#define FLTEE_AEAD_REPORT 1
+#define FLTEE_AEAD_DROP 2
+void fltee_set_upload_aead_policy(int policy, size_t min_survivors /* 0 = 1 */);
+/* The verdict of the last authenticated ECALL of fl_id under REPORT / DROP (either ECALL; it
+ * is overwritten by every such call, a clean one stores an empty list, and ecall_fl_init of
+ * that fl_id forgets it): the failed client ids in upload order into failed_ids[0 .. cap);
+ * *n_failed is the full count even when cap is smaller; *round = the round that call was for.
+ * Nothing stored (ABORT, AEAD off, no call yet): *n_failed = 0 and *round = the config's
+ * current round.  FLTEE_ERROR_UNEXPECTED (0x1) for an unknown fl_id, answered before the eid
+ * is looked at (the configs are process-wide); 0x2 for a null n_failed. */
+fltee_status_t fltee_auth_report(fltee_eid_t eid, uint32_t fl_id, uint32_t *round,
+                                 uint32_t *failed_ids, size_t cap, size_t *n_failed);
+/* The survivors gather, device-resident: d_out[s][0 .. k) = d_records[d_keep[s]][0 .. k) for
+ * s < n_keep, on n x k records of 8 bytes; d_keep (ascending client positions) is device
+ * memory; d_out must not overlap d_records (never in place: with client 0 dropped slice s of
+ * the output lies over slice s - 1 of the input).  16-byte loads and stores where a source
+ * and a destination slice agree modulo 16, 8-byte records otherwise.  Asynchronous on
+ * `stream`; n_keep = 0 writes nothing.  Refused with FLTEE_ERROR_INVALID_PARAMETER by host
+ * arithmetic, before any device call: a null pointer, n_keep > n, k == 0, n * k >= 2^31.  A
+ * d_keep[s] >= n is clamped (nothing is read out of bounds) and ORs FLTEE_DEV_ERR_LAUNCH into
+ * the library's status word (fltee_device_status). */
+fltee_status_t fltee_gather_clients_device(const void *d_records, size_t n, size_t k,
+                                           const uint32_t *d_keep, size_t n_keep, void *d_out,
+                                           void *stream);
+
 /* out[j] = coef * sum_r rows[r*d + j], rows added in order (exact fp32): the
  * root-side combine of per-GPU partial sums, in the batch order of alg 6
  * (lib.rs:564-573: global[i] += batch_sum[i], then average). */
