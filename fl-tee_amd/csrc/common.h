@@ -156,6 +156,19 @@ hipError_t launch_scale(float *out, size_t d, float coef, hipStream_t s);
 hipError_t launch_check_range(const void *rec, size_t nrec, uint32_t limit, uint32_t *status,
                               hipStream_t s);
 
+// k_packed.hip: packed dense slices — n rows of 2 * ceil(d / 2) f32: a client's d values in
+// position order, then one ignored f32 when d is odd.  The packed accumulate has
+// launch_dense_accumulate's contract without the status word (there is no index to check);
+// clip_coef: launch_client_clip_coef's coefficients from a packed row; unpack: rows ->
+// n * d records (j, v[j]); pack: values [n][d] -> rows (padding +0.0).
+hipError_t launch_dense_accumulate_packed(const void *packed, size_t n, size_t d, float coef, float *out,
+                                          const float *client_coef, bool accumulate, hipStream_t s);
+hipError_t launch_packed_clip_coef(const void *packed, size_t n, size_t d, float clipping, float *coef,
+                                   hipStream_t s);
+hipError_t launch_unpack_dense(const void *packed, size_t n, size_t d, uint64_t *rec, hipStream_t s);
+hipError_t launch_pack_dense(const float *values, size_t n, size_t d, void *packed, hipStream_t s);
+void set_packed_variant(int v);
+
 // k_bitonic.hip
 // valid: positions >= valid hold identical pad records (0: unknown); the stage blocks
 // made of pads alone are skipped (exact, data-independent)

@@ -138,6 +138,17 @@ struct AuthReport {
 };
 static std::map<uint32_t, AuthReport> g_auth_reports;
 
+// ---- packed dense uploads (fltee_set_upload_packed; k_packed.hip) ---------------------
+static bool g_upload_packed = false;
+
+// The packed-call rule (include/fltee_agg.h fltee_upload_is_packed): the switch is on, the
+// request declares a dense upload of d >= 2 parameters, and every client's ciphertext is
+// exactly one packed slice (ct_bytes: 0 when the payload is not n equal slices).  d = 1 is
+// never packed: there a packed slice and a record are the same 8 bytes.
+static bool upload_is_packed(bool on, size_t d, size_t k_req, size_t ct_bytes) {
+    return on && d >= 2 && (k_req == 0 || k_req == d) && ct_bytes / 8 == (d + 1) / 2 && ct_bytes % 8 == 0;
+}
+
 static bool keeps_verdict(bool aead) { return aead && g_aead_policy != FLTEE_AEAD_ABORT; }
 
 // fail: the n fail words as load_and_decrypt read them back (the word gathering them behind)
@@ -165,7 +176,8 @@ static inline void put_be32(uint8_t *p, uint32_t v) {
 }
 
 // What the ECALLs bind: IV = BE32(fl_id) || BE32(round) || BE32(0), AAD = BE32(fl_id) ||
-// BE32(round) || BE32(client_id) || BE32(aggregation_alg)
+// BE32(round) || BE32(client_id) || BE32(aggregation_alg) — alg: a packed call passes
+// aggregation_alg | FLTEE_AAD_PACKED_BIT, so a slice sealed for one format fails under the other
 static void ecall_gcm_args(uint32_t fl_id, uint32_t round, const uint32_t *ids, size_t n,
                            uint32_t alg, GcmArgs &g) {
     put_be32(g.iv, fl_id);
@@ -333,8 +345,10 @@ static bool ecall_takes_tree(uint32_t alg, size_t n, size_t rpc, size_t d) {
 
 // The options aggregate_records gives aggregate() for an ECALL's alg (shared with the
 // staged path below).
+// rpc: the records per client the aggregate sees (a packed call: d); packed: c->records holds
+// packed slices (FLTEE_OPT_PACKED)
 static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d, size_t k_req,
-                                    size_t batch, uint64_t seed) {
+                                    size_t batch, uint64_t seed, bool packed = false) {
     fltee_device_opts o;
     std::memset(&o, 0, sizeof o);
     o.k_req = k_req;
@@ -343,6 +357,7 @@ static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d
     const bool flat = alg == FLTEE_ALG_BASELINE || alg == FLTEE_ALG_PATH_ORAM ||
                       alg == FLTEE_ALG_NON_OBLIVIOUS;
     if (flat && rpc == d) o.flags |= FLTEE_OPT_DENSE;
+    if (packed) o.flags |= FLTEE_OPT_PACKED;
     if (ecall_takes_tree(alg, n, rpc, d)) o.flags |= FLTEE_OPT_ORAM_TREE;
     if (alg == FLTEE_ALG_NIPS19) o.seed = seed ? seed : next_seed();
     // advanced's fold (advanced.rs:66-101) runs once with halo = n: bit for bit for every
@@ -385,8 +400,8 @@ static uint32_t status_to_retval(uint32_t dev_st, uint32_t alg, bool *retry) {
 // rec: the records when they are not c->records (the survivors of a DROP call).
 static uint32_t aggregate_records(DeviceCtx *c, uint32_t alg, size_t n, size_t rpc, size_t d,
                                   size_t k_req, size_t batch, float *d_out, uint64_t seed = 0,
-                                  const void *rec = nullptr) {
-    fltee_device_opts o = ecall_opts(alg, n, rpc, d, k_req, batch, seed);
+                                  const void *rec = nullptr, bool packed = false) {
+    fltee_device_opts o = ecall_opts(alg, n, rpc, d, k_req, batch, seed, packed);
     if (alg == FLTEE_ALG_OPTIMIZED) o.flags &= ~FLTEE_OPT_K_REQ;
     if (!rec) rec = c->records.ptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -469,9 +484,11 @@ static hipError_t launch_copy_out(const void *src, void *dst, size_t bytes, hipS
 
 static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, size_t n,
                              const uint8_t *enc, size_t bpc, size_t d, size_t k_req, size_t batch,
-                             uint64_t seed, const FLConfig &cfg, float *host_out, float *times) {
+                             uint64_t seed, const FLConfig &cfg, float *host_out, float *times,
+                             bool packed = false) {
     const double t0 = now_s();
-    const size_t rpc = bpc / 8;
+    const size_t rpc = bpc / 8;                // 8-byte units per client as decrypted
+    const size_t rpa = packed ? d : rpc;       // records per client as aggregated
     const size_t rkb = (n * 44 * 4 + 15) / 16 * 16, cb = n * bpc;
     const size_t d4 = (d * 4 + 15) / 16 * 16;
     const bool zero_copy = 16 + rkb + cb <= kZeroCopyBytes;
@@ -498,8 +515,8 @@ static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, si
         (!zero_copy && fl_memcpy_async(stage + d4 + 16, enc, cb, hipMemcpyHostToDevice, s) != hipSuccess) ||
         (!cb && fl_memset_async(d_st, 0, 4, s) != hipSuccess))
         return FLTEE_ERROR_UNEXPECTED;
-    fltee_device_opts o = ecall_opts(alg == FLTEE_ALG_OPTIMIZED ? FLTEE_ALG_ADVANCED : alg, n, rpc, d,
-                                     k_req, batch, seed);
+    fltee_device_opts o = ecall_opts(alg == FLTEE_ALG_OPTIMIZED ? FLTEE_ALG_ADVANCED : alg, n, rpa, d,
+                                     k_req, batch, seed, packed);
     if (alg == FLTEE_ALG_OPTIMIZED) o.flags &= ~FLTEE_OPT_K_REQ;
     // the call's device work: AES (timed by events) -> aggregation (-> DP) -> copy-out
     auto enqueue = [&](bool retry_pass) -> uint32_t {
@@ -510,7 +527,7 @@ static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, si
                         hipSuccess) ||
              hipEventRecord(c->call_ev[2], s) != hipSuccess))
             return FLTEE_ERROR_UNEXPECTED;
-        const uint32_t a = aggregate(alg, c->records.ptr, n, rpc, d, d_out, o, s, d_st);
+        const uint32_t a = aggregate(alg, c->records.ptr, n, rpa, d, d_out, o, s, d_st);
         if (a != FLTEE_SUCCESS) return a;
         if (cfg.dp && launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n, next_seed(), s) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
@@ -708,11 +725,18 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     if (aead && (bpc < FLTEE_GCM_TAG_BYTES || encrypted_parameters_size % n ||
                  !gcm_sizes_ok(bpc - FLTEE_GCM_TAG_BYTES, 16)))
         return fail(FLTEE_ERROR_INVALID_PARAMETER);
-    const size_t rpc = (aead ? bpc - FLTEE_GCM_TAG_BYTES : bpc) / 8;
+    const size_t ctb = aead ? bpc - FLTEE_GCM_TAG_BYTES : bpc;
+    // packed dense slices (fltee_set_upload_packed): loaded, decrypted, verified and gathered
+    // as rpc = ceil(d / 2) 8-byte units per client, aggregated as rpa = d records
+    const bool packed = upload_is_packed(g_upload_packed, d, num_of_sparse_parameters,
+                                         encrypted_parameters_size % n ? 0 : ctb);
+    const size_t rpc = ctb / 8;
+    const size_t rpa = packed ? d : rpc;
     GcmArgs gcm;
-    if (aead) ecall_gcm_args(fl_id, round, client_ids, n, aggregation_alg, gcm);
+    if (aead)
+        ecall_gcm_args(fl_id, round, client_ids, n, aggregation_alg | (packed ? FLTEE_AAD_PACKED_BIT : 0u), gcm);
     if ((aggregation_alg == FLTEE_ALG_ADVANCED || aggregation_alg == FLTEE_ALG_BUBBLE) &&
-        n * num_of_sparse_parameters > n * rpc)
+        n * num_of_sparse_parameters > n * rpa)
         return fail(FLTEE_ERROR_INVALID_PARAMETER);  // advanced.rs:72 out-of-bounds panic
 
     if (!c->outbuf.reserve(d * 4 + 16)) return fail(FLTEE_ERROR_OUT_OF_MEMORY);
@@ -742,8 +766,9 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     bool group_tried = false;  // a shape the group declined (or failed on) is not offered to it again
     const bool flat = aggregation_alg == FLTEE_ALG_BASELINE || aggregation_alg == FLTEE_ALG_PATH_ORAM ||
                       aggregation_alg == FLTEE_ALG_NON_OBLIVIOUS;
-    const bool tree = ecall_takes_tree(aggregation_alg, n, rpc, d);
-    if (G && flat && !tree && rpc == d && bpc == d * 8 + tagb) {
+    const bool tree = ecall_takes_tree(aggregation_alg, n, rpa, d);
+    // (a packed call is loaded on the root: the dense group path shards records by column)
+    if (G && flat && !tree && !packed && rpc == d && bpc == d * 8 + tagb) {
         // dense uploads over a multi-GPU eid: every GPU loads and decrypts its own
         // parameter range (group.hip); "Loading" = the parallel H2D, "Decryption" = the
         // decrypt + aggregate + gather.  Authenticated: every GPU also hashes its range, the
@@ -766,12 +791,12 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     // (alg 7, once the host has opted in, shards like advanced: the same fold and tail)
     const bool sharded = G && (((aggregation_alg == FLTEE_ALG_ADVANCED ||
                                  (aggregation_alg == FLTEE_ALG_BUBBLE && bubble_ecall_default())) &&
-                                k_req == rpc && !exact_runs_default()) ||
+                                k_req == rpa && !exact_runs_default()) ||
                                aggregation_alg == FLTEE_ALG_NIPS19);
     // nips19 draws its seed (Laplace counts, shuffle key) once per call, whichever path
     // runs it, so a multi-GPU eid consumes the seed sequence exactly as one GPU does
     const uint64_t seed = aggregation_alg == FLTEE_ALG_NIPS19 ? next_seed() : 0;
-    if (st == FLTEE_GROUP_FALLBACK && sharded && !group_tried && group_splits_host_copy(G)) {
+    if (st == FLTEE_GROUP_FALLBACK && sharded && !group_tried && !packed && group_splits_host_copy(G)) {
         // every GPU copies and decrypts (authenticated: and verifies) the clients of its own
         // position range
         std::vector<uint32_t> rk;
@@ -800,7 +825,7 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         // one GPU, a small payload: one DMA each way, one host synchronisation (an
         // authenticated upload needs the fail word before the aggregation: the path below)
         st = staged_ecall(c, aggregation_alg, client_ids, n, encrypted_parameters_data, bpc, d, k_req,
-                          0, seed, cfg, updated_parameters_data, execution_time_results);
+                          0, seed, cfg, updated_parameters_data, execution_time_results, packed);
         if (st) {
             std::memset(updated_parameters_data, 0, d * sizeof(float));
             std::memset(execution_time_results, 0, 3 * sizeof(float));
@@ -832,15 +857,25 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         GroupInput in;
         in.root_rec = (const uint64_t *)c->records.ptr;
         if (sharded && !group_tried && n_agg == n) {
+            if (packed) {
+                // the position-range routes shard records: the root unpacks its rows into the
+                // engine's record scratch (no aggregate runs on the root before the ranks have
+                // taken their ranges) and the group proceeds as after any root load
+                if (!c->ws_rec.reserve(n * d * 8)) return fail(FLTEE_ERROR_OUT_OF_MEMORY);
+                if (launch_unpack_dense(c->records.ptr, n, d, (uint64_t *)c->ws_rec.ptr, c->stream) != hipSuccess ||
+                    fl_stream_sync(c->stream) != hipSuccess)
+                    return fail(FLTEE_ERROR_UNEXPECTED);
+                in.root_rec = (const uint64_t *)c->ws_rec.ptr;
+            }
             if (aggregation_alg == FLTEE_ALG_ADVANCED)
-                st = group_advanced(G, in, n, rpc, d, coef, d_out);
+                st = group_advanced(G, in, n, rpa, d, coef, d_out);
             else if (aggregation_alg == FLTEE_ALG_BUBBLE)
-                st = group_bubble(G, in, n, rpc, d, coef, d_out);
+                st = group_bubble(G, in, n, rpa, d, coef, d_out);
             else
-                st = group_nips19(G, c, in, n, rpc, k_req, d, seed, coef, d_out);
+                st = group_nips19(G, c, in, n, rpa, k_req, d, seed, coef, d_out);
         }
         if (st == FLTEE_GROUP_FALLBACK)  // one device (or a shape the group does not shard)
-            st = aggregate_records(c, aggregation_alg, n_agg, rpc, d, k_req, 0, d_out, seed, rec);
+            st = aggregate_records(c, aggregation_alg, n_agg, rpa, d, k_req, 0, d_out, seed, rec, packed);
     }
     if (!st && cfg.dp) {  // lib.rs:399-408
         if (launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n_agg, next_seed(), c->stream) != hipSuccess)
@@ -1207,6 +1242,15 @@ extern "C" fltee_status_t fltee_debug_ghash_window_host(uint32_t client_id, cons
 extern "C" void fltee_set_upload_aead(int on) {
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
     g_upload_aead = on != 0;
+}
+
+extern "C" void fltee_set_upload_packed(int on) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    g_upload_packed = on != 0;
+}
+
+extern "C" int fltee_upload_is_packed(int on, size_t d, size_t k_req, size_t ct_bytes) {
+    return upload_is_packed(on != 0, d, k_req, ct_bytes) ? 1 : 0;
 }
 
 extern "C" void fltee_set_upload_aead_policy(int policy, size_t min_survivors) {

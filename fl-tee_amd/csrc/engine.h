@@ -45,6 +45,7 @@ enum Route : uint32_t {
     kRouteBubble,        // alg 7: the stable network, then advanced's tail
     kRouteOptimized,     // alg 6: advanced per batch
     kRouteNips19,
+    kRoutePacked,        // flat algs, FLTEE_OPT_PACKED: the packed accumulate (k_packed.hip)
 };
 enum Tail : uint32_t {
     kTailNone,
@@ -73,6 +74,7 @@ struct Plan {
     fltee_status_t status = FLTEE_SUCCESS;  // else the refusal; the sizes are still filled in
     Route route = kRouteNone;
     bool clip_records = false;  // FLTEE_OPT_CLIP works on a clipped copy of the records
+    bool unpack = false;        // FLTEE_OPT_PACKED off the packed route: the records are unpacked into ws_rec
     AdvShape adv;               // advanced, alg 7, an alg-6 batch, the lazy tree's readout (1 x slots)
     AdvShape adv_last;          // alg 6: the short last batch (when n % batch)
     size_t batch = 0;           // alg 6

@@ -236,12 +236,14 @@ static void plan_adv_bytes(Plan &p, const AdvShape &a) {
 
 static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
     Plan p;
-    const bool dense = (o.flags & FLTEE_OPT_DENSE) != 0;
+    // a packed upload (FLTEE_OPT_PACKED) is a dense one: n rows of values, k == d >= 2
+    const bool packed = (o.flags & FLTEE_OPT_PACKED) != 0;
+    const bool dense = packed || (o.flags & FLTEE_OPT_DENSE) != 0;
     const bool tree = alg == FLTEE_ALG_PATH_ORAM && (o.flags & FLTEE_OPT_ORAM_TREE);
     const size_t nrec = n * k, k_req = (o.flags & FLTEE_OPT_K_REQ) ? o.k_req : k;
     auto refuse_if = [&p](bool bad) { if (bad) p.status = FLTEE_ERROR_INVALID_PARAMETER; };
     // 32-bit positions; a dense upload has one record per parameter
-    refuse_if(n == 0 || nrec + d >= ((size_t)1 << 31) || (dense && k != d));
+    refuse_if(n == 0 || nrec + d >= ((size_t)1 << 31) || (dense && k != d) || (packed && d < 2));
     switch (alg) {
     case FLTEE_ALG_PATH_ORAM:
     case FLTEE_ALG_BASELINE:
@@ -260,7 +262,7 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
             // "client" of `slots` records: each index at most once, runs of <= 2 entries)
             if (lazy) plan_adv_bytes(p, p.adv = adv_shape(1, p.tree_slots, d, p.tree_slots, 1));
         } else if (dense) {
-            p.route = kRouteDense;
+            p.route = packed ? kRoutePacked : kRouteDense;
         } else if (alg == FLTEE_ALG_NON_OBLIVIOUS && use_scatter_rows(n, k, d)) {
             p.route = kRouteScatterRows;
             p.bytes[kWsMat] = n * d * 4;
@@ -320,9 +322,13 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
         // every route but the dense accumulate (which takes the coefficients) reads records:
         // FLTEE_OPT_DENSE on algs 1, 2, 6, 7 and on the tree only asserts k == d
         p.bytes[kWsCoef] = n * 4;
-        p.clip_records = p.route != kRouteDense;
+        p.clip_records = p.route != kRouteDense && p.route != kRoutePacked;
         if (p.clip_records) p.bytes[kWsRec] = nrec * 8;
     }
+    // every route but the packed accumulate reads records: the plan (n, d, d) has, on the
+    // rows unpacked into the record scratch (where FLTEE_OPT_CLIP then clips them in place)
+    p.unpack = packed && p.route != kRoutePacked;
+    if (p.unpack) p.bytes[kWsRec] = nrec * 8;
     return p;
 }
 
@@ -520,15 +526,25 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     const size_t n_avg = o.n_avg ? o.n_avg : n;
     const float coef = (o.flags & FLTEE_OPT_NO_AVERAGE) ? 1.0f : 1.0f / (float)n_avg;
 
+    // packed rows off the packed route: every alg below runs on the records (j, v[j])
+    if (p.unpack) {
+        if (launch_unpack_dense(rec, n, d, (uint64_t *)c->ws_rec.ptr, s) != hipSuccess)
+            return FLTEE_ERROR_UNEXPECTED;
+        rec = c->ws_rec.ptr;
+    }
+
     // per-client L2 clip (update.py:187-204), off by default
     const float *ccoef = nullptr;
     if (o.flags & FLTEE_OPT_CLIP) {
         float *cf = (float *)c->ws_coef.ptr;
-        if (launch_client_clip_coef(rec, n, k, o.clipping, cf, s) != hipSuccess)
+        if ((p.route == kRoutePacked ? launch_packed_clip_coef(rec, n, d, o.clipping, cf, s)
+                                     : launch_client_clip_coef(rec, n, k, o.clipping, cf, s)) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
         ccoef = cf;
         if (p.clip_records) {
-            if (fl_memcpy_async(c->ws_rec.ptr, rec, n * k * 8, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            // (an unpacked copy is already the scratch: clipped where it is)
+            if ((!p.unpack &&
+                 fl_memcpy_async(c->ws_rec.ptr, rec, n * k * 8, hipMemcpyDeviceToDevice, s) != hipSuccess) ||
                 launch_apply_clip(c->ws_rec.ptr, n, k, cf, s) != hipSuccess)
                 return FLTEE_ERROR_UNEXPECTED;
             rec = c->ws_rec.ptr;
@@ -553,6 +569,9 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     }
     case kRouteDense:
         e = launch_dense_accumulate(rec, n, d, coef, out, ccoef, acc, status, s);
+        break;
+    case kRoutePacked:
+        e = launch_dense_accumulate_packed(rec, n, d, coef, out, ccoef, acc, s);
         break;
     case kRouteScatterRows:
         if (c->mat_clean_ptr != c->ws_mat.ptr || c->mat_clean_cap != c->ws_mat.cap) {
@@ -1099,6 +1118,27 @@ extern "C" size_t fltee_debug_net_log(size_t i, char *name, size_t name_cap, uin
     return nl;
 }
 
+// ---- packed dense slices (k_packed.hip) ----------------------------------
+extern "C" size_t fltee_packed_slice_bytes(size_t d) { return (d + 1) / 2 * 8; }
+
+extern "C" fltee_status_t fltee_unpack_dense_device(const void *d_packed, size_t n, size_t d,
+                                                    void *d_records, void *stream) {
+    if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_packed || !d_records)
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    return launch_unpack_dense(d_packed, n, d, (uint64_t *)d_records, (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_client_pack_dense_device(const float *d_values, size_t n, size_t d,
+                                                         void *d_packed, void *stream) {
+    if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_values || !d_packed)
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    return launch_pack_dense(d_values, n, d, d_packed, (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
 extern "C" fltee_status_t fltee_sum_rows_device(const float *d_rows, size_t nrows, size_t d,
                                                 float coef, float *d_out, void *stream) {
     if (nrows == 0) return FLTEE_ERROR_INVALID_PARAMETER;
@@ -1133,6 +1173,8 @@ extern "C" int fltee_debug_read_floor(const void *d_src, size_t bytes, void *d_s
 }
 // tuning hook (not part of the public header)
 extern "C" void fltee_debug_set_dense_variant(int v) { fltee::set_dense_variant(v); }
+// tuning hook: the packed accumulate's A/B launch shapes (k_packed.hip; 0 = shipped)
+extern "C" void fltee_debug_set_packed_variant(int v) { fltee::set_packed_variant(v); }
 // A/B hook: 0 runs advanced's second bitonic sort instead of the compaction network
 extern "C" void fltee_debug_set_advanced_compaction(int on) { fltee::g_advanced_compaction = on != 0; }
 extern "C" void fltee_debug_set_compact_variant(int v) { fltee::set_compact_variant(v); }

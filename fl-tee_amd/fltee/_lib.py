@@ -46,6 +46,8 @@ OPT_NO_AVERAGE = 0x10
 OPT_K_REQ = 0x20
 OPT_ORAM_TREE = 0x40
 OPT_ORAM_LAZY = 0x80
+OPT_PACKED = 0x100  # d_records: packed dense slices (value-only rows of 2 * ceil(d / 2) f32)
+AAD_PACKED_BIT = 0x80000000  # FLTEE_AAD_PACKED_BIT: a packed call's last AAD word is alg | this
 
 
 class DeviceOpts(ctypes.Structure):
@@ -87,6 +89,11 @@ SIGNATURES = {
     "fltee_gcm_finish_device": (_U32, [_P, _S, _P, _S, _P, _S, _P, _P, _P]),
     "fltee_decrypt_slice_auth_device": (_U32, [_P, _S, _P, _S, _S, _S, _P, _P, _P]),
     "fltee_debug_ghash_window_host": (_U32, [_U32, _P, _S, ctypes.c_int, _P, _S, _S, _S, _P]),
+    "fltee_packed_slice_bytes": (_S, [_S]),
+    "fltee_upload_is_packed": (ctypes.c_int, [ctypes.c_int, _S, _S, _S]),
+    "fltee_set_upload_packed": (None, [ctypes.c_int]),
+    "fltee_unpack_dense_device": (_U32, [_P, _S, _S, _P, _P]),
+    "fltee_client_pack_dense_device": (_U32, [_P, _S, _S, _P, _P]),
     "fltee_set_upload_aead": (None, [ctypes.c_int]),
     "fltee_set_upload_aead_policy": (None, [ctypes.c_int, _S]),
     "fltee_auth_report": (_U32, [_U64, _U32, _P, _P, _S, _P]),
@@ -137,6 +144,7 @@ EXTRA_SIGNATURES = {  # test hooks not in the public header
     "fltee_debug_gcm_subkeys": (ctypes.c_int, [_U32, _P, _P, ctypes.c_int]),
     "fltee_debug_gcm_segment_blocks": (_S, []),
     "fltee_debug_set_dense_variant": (None, [ctypes.c_int]),
+    "fltee_debug_set_packed_variant": (None, [ctypes.c_int]),
     "fltee_debug_set_oram_bucket": (None, [ctypes.c_int]),
     "fltee_debug_set_aes_variant": (None, [ctypes.c_int]),
     "fltee_debug_read_floor": (ctypes.c_int, [_P, _S, _P, ctypes.c_uint, _P]),

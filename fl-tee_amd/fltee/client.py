@@ -54,6 +54,18 @@ def serialize_dense(values, stream=None):
     return rec
 
 
+def pack_dense(values, stream=None):
+    """[n, d] -> f32 [n, 2 * ceil(d / 2)]: the packed dense slices (fltee.ecalls.
+    set_upload_packed) — each client's d values in position order, then one +0.0 when d is odd;
+    half the bytes of serialize_dense."""
+    v = _values(values)
+    n, d = v.shape
+    out = torch.empty((n, (d + 1) // 2 * 2), dtype=torch.float32, device=v.device)
+    _check(L.lib().fltee_client_pack_dense_device(_ptr(v), n, d, _ptr(out), _stream(stream)),
+           "fltee_client_pack_dense_device")
+    return out
+
+
 def l2clipping(records, n, k, clipping, stream=None):
     """In place on n clients x k records: val *= min(1, clipping / ||values||_2)."""
     assert records.is_cuda and records.dtype == torch.int64 and records.numel() >= n * k
@@ -81,11 +93,14 @@ def ecall_iv(fl_id, round_):
     return struct.pack(">III", fl_id, round_, 0)
 
 
-def ecall_aad(fl_id, round_, client_ids, aggregation_alg):
+def ecall_aad(fl_id, round_, client_ids, aggregation_alg, packed=False):
     """The ECALLs' AAD, 16 bytes per client: BE32(fl_id) || BE32(round) || BE32(client_id) ||
     BE32(aggregation_alg) — a slice cannot be replayed in another round, moved to another
-    client or submitted under another algorithm."""
-    return b"".join(struct.pack(">IIII", fl_id, round_, int(c), aggregation_alg) for c in client_ids)
+    client or submitted under another algorithm.  packed: the slices are packed dense values
+    (pack_dense); the last word is BE32(aggregation_alg | 0x80000000), so a slice sealed as
+    records never verifies as packed values, nor the other way round."""
+    word = aggregation_alg | (L.AAD_PACKED_BIT if packed else 0)
+    return b"".join(struct.pack(">IIII", fl_id, round_, int(c), word) for c in client_ids)
 
 
 def encrypt_parameters_gcm(records, client_ids, iv, aad=b"", stream=None):
@@ -105,19 +120,29 @@ def encrypt_parameters_gcm(records, client_ids, iv, aad=b"", stream=None):
     return out.reshape(n, B + L.GCM_TAG_BYTES)
 
 
-def encrypt_parameters_auth(records, client_ids, fl_id, round_, aggregation_alg, stream=None):
+def encrypt_parameters_auth(records, client_ids, fl_id, round_, aggregation_alg, stream=None,
+                            packed=False):
     """The authenticated upload of an ECALL (fltee.ecalls.set_upload_aead): the payload of
-    ecall_secure_aggregation(fl_id, round_, client_ids, ..., aggregation_alg)."""
+    ecall_secure_aggregation(fl_id, round_, client_ids, ..., aggregation_alg).  packed:
+    `records` is pack_dense's tensor (any tensor is sealed by its bytes, n equal parts)."""
     return encrypt_parameters_gcm(records, client_ids, ecall_iv(fl_id, round_),
-                                  ecall_aad(fl_id, round_, client_ids, aggregation_alg),
+                                  ecall_aad(fl_id, round_, client_ids, aggregation_alg, packed),
                                   stream).reshape(-1)
 
 
-def produce_payloads(values, client_ids, k=None, clipping=None, stream=None):
-    """fl_main.py:221-238 for every client at once: k=None -> dense uploads."""
+def produce_payloads(values, client_ids, k=None, clipping=None, stream=None, packed=False):
+    """fl_main.py:221-238 for every client at once: k=None -> dense uploads; packed (dense
+    only): value-only slices of 8 * ceil(d / 2) bytes per client (pack_dense), for a server
+    with fltee.ecalls.set_upload_packed(True)."""
     v = _values(values)
     n, d = v.shape
     assert len(client_ids) == n
+    if packed:
+        assert k is None or k == d, "packed uploads are dense"
+        if clipping is not None:  # clipped as records (the reference's arithmetic), then packed
+            rec = l2clipping(serialize_dense(v, stream), n, d, clipping, stream)
+            v = rec.view(torch.float32).reshape(n, d, 2)[:, :, 1].contiguous()
+        return encrypt_parameters(pack_dense(v, stream), client_ids, stream)
     if k is None:
         rec, kk = serialize_dense(v, stream), d
     else:

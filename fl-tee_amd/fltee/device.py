@@ -38,11 +38,12 @@ def unpack_records(rec):
 
 def opts(*, dense=False, dp=False, clip=False, accumulate=False, no_average=False, sigma=1.12,
          clipping=1.0, seed=0, k_req=None, batch=0, n_avg=0, fold_halo=0, status=None,
-         oram_tree=False, oram_lazy=False):
+         oram_tree=False, oram_lazy=False, packed=False):
     o = L.DeviceOpts()
     o.flags = ((L.OPT_DENSE if dense else 0) | (L.OPT_DP if dp else 0) | (L.OPT_CLIP if clip else 0)
                | (L.OPT_ACCUMULATE if accumulate else 0) | (L.OPT_NO_AVERAGE if no_average else 0)
-               | (L.OPT_ORAM_TREE if oram_tree else 0) | (L.OPT_ORAM_LAZY if oram_lazy else 0))
+               | (L.OPT_ORAM_TREE if oram_tree else 0) | (L.OPT_ORAM_LAZY if oram_lazy else 0)
+               | (L.OPT_PACKED if packed else 0))
     o.sigma, o.clipping, o.seed = sigma, clipping, seed
     if k_req is not None:
         o.flags |= L.OPT_K_REQ
@@ -58,8 +59,13 @@ def _check(st, what):
 
 
 def aggregate(alg, records, n, k, d, out=None, stream=None, **kw):
-    """fltee_aggregate_device: aggregate n x k records (int64 cuda tensor) into out[d] (f32)."""
-    assert records.is_cuda and records.dtype == torch.int64 and records.numel() >= n * k
+    """fltee_aggregate_device: aggregate n x k records (int64 cuda tensor) into out[d] (f32).
+    packed=True: records is n packed slices instead (any cuda tensor of n * packed_row(d)
+    f32's worth of bytes: client c's d values, then one ignored f32 when d is odd; k == d)."""
+    if kw.get("packed"):
+        assert records.is_cuda and records.numel() * records.element_size() >= n * packed_row(d) * 4
+    else:
+        assert records.is_cuda and records.dtype == torch.int64 and records.numel() >= n * k
     if out is None:
         out = torch.empty(d, dtype=torch.float32, device=records.device)
     o = opts(**kw)
@@ -67,6 +73,23 @@ def aggregate(alg, records, n, k, d, out=None, stream=None, **kw):
                                         _stream(stream))
     _check(st, "fltee_aggregate_device")
     return out
+
+
+def packed_row(d):
+    """f32 slots of one packed slice of d parameters: 2 * ceil(d / 2)."""
+    return (d + 1) // 2 * 2
+
+
+def unpack_dense(packed, n, d, records=None, stream=None):
+    """fltee_unpack_dense_device: n packed slices ([n, packed_row(d)] f32) -> int64 records
+    [n * d]: (j, v[j]) per client."""
+    assert packed.is_cuda and packed.is_contiguous()
+    assert packed.numel() * packed.element_size() >= n * packed_row(d) * 4
+    if records is None:
+        records = torch.empty(n * d, dtype=torch.int64, device=packed.device)
+    _check(L.lib().fltee_unpack_dense_device(_ptr(packed), n, d, _ptr(records), _stream(stream)),
+           "fltee_unpack_dense_device")
+    return records
 
 
 def reserve(alg, n, k, d, **kw):

@@ -144,6 +144,21 @@ def set_upload_aead(on):
     _upload_aead = bool(on)
 
 
+def set_upload_packed(on):
+    """Packed dense uploads (fltee_set_upload_packed; off by default): while on, an
+    ecall_secure_aggregation call whose request declares a dense upload (num_of_sparse_parameters
+    0 or d, d >= 2) and whose clients each send exactly 8 * ceil(d / 2) ciphertext bytes (plus
+    the tag under AEAD) is read as value-only slices (fltee.client.pack_dense /
+    produce_payloads(packed=True)): half the bytes, the same [out] bit for bit.  Every other
+    call — a dense 8 * d-byte upload too — is read as records, as before."""
+    L.lib().fltee_set_upload_packed(1 if on else 0)
+
+
+def upload_is_packed(on, d, k_req, ct_bytes):
+    """fltee_upload_is_packed: the packed-call rule on one client's ciphertext bytes."""
+    return bool(L.lib().fltee_upload_is_packed(1 if on else 0, d, k_req, ct_bytes))
+
+
 AEAD_POLICIES = {"abort": L.AEAD_ABORT, "report": L.AEAD_REPORT, "drop": L.AEAD_DROP}
 
 

@@ -9,6 +9,7 @@ code); the handlers are fltee.server.Aggregator, the server.rs logic over the C 
     python -m fltee.grpc_server [--address 0.0.0.0:50051] [--device 0] [--dp]
                                 [--strict-reference] [--quiet]
                                 [--aead [--aead-policy abort|report|drop]]
+                                [--packed-dense]
 
 Like the reference: verbose on, dp off (server.rs:236-237; --dp turns DP on for
 the configs[3] runs), one enclave per process; calls are serialised by the
@@ -122,13 +123,17 @@ def main(argv=None):
                          "log the failed clients, or aggregate the verified clients")
     ap.add_argument("--aead-min-survivors", type=int, default=1,
                     help="--aead-policy drop: verified clients needed to answer the round")
+    ap.add_argument("--packed-dense", action="store_true",
+                    help="accept packed dense uploads: value-only slices of 8 * ceil(d / 2) bytes "
+                         "per client (uploads of records are still answered as before)")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     if args.aead_policy is not None and not args.aead:
         ap.error("--aead-policy needs --aead")
     agg = Aggregator(device=args.device, verbose=not args.quiet, dp=args.dp,
                      strict_reference=args.strict_reference, aead=args.aead,
-                     aead_policy=args.aead_policy or "abort", min_survivors=args.aead_min_survivors)
+                     aead_policy=args.aead_policy or "abort", min_survivors=args.aead_min_survivors,
+                     packed=args.packed_dense)
     server, port = make_server(agg, args.address, verbose=not args.quiet)
     server.start()
     print(f"[Server] Now GRPC Server is binded on {args.address} (port {port})", flush=True)

@@ -19,11 +19,15 @@ request).  Documented deviations from the reference host:
     "drop": the verified clients are aggregated (the averages take their count) as long as
     `min_survivors` of them verified, the failed ones kept and logged the same way.  The
     reply has no field for the list (the proto is unchanged): the host reads it here.
+  * `packed=True` (off by default) accepts packed dense uploads: a request that declares a
+    dense upload and carries 8 * ceil(d / 2) bytes per client (value-only slices,
+    fltee.client.pack_dense) is aggregated from half the bytes, with the same reply; every
+    other request, a dense 8 * d-byte one too, is answered as before.
 """
 import time
 
 from . import _lib as L
-from .ecalls import AEAD_POLICIES, Enclave, set_upload_aead, set_upload_aead_policy
+from .ecalls import AEAD_POLICIES, Enclave, set_upload_aead, set_upload_aead_policy, set_upload_packed
 
 
 class ServerPanic(RuntimeError):
@@ -32,7 +36,7 @@ class ServerPanic(RuntimeError):
 
 class Aggregator:
     def __init__(self, device=0, verbose=False, dp=False, strict_reference=False, enclave=None,
-                 aead=False, aead_policy="abort", min_survivors=1):
+                 aead=False, aead_policy="abort", min_survivors=1, packed=False):
         if aead_policy not in AEAD_POLICIES:
             raise ValueError(f"aead_policy must be one of {sorted(AEAD_POLICIES)}")
         if aead_policy != "abort" and not aead:
@@ -44,6 +48,9 @@ class Aggregator:
         if self.aead:  # process-wide, like the enclave's other start-up switches
             set_upload_aead(True)
             set_upload_aead_policy(aead_policy, min_survivors)
+        self.packed = bool(packed)
+        if self.packed:  # process-wide too
+            set_upload_packed(True)
         self.verbose = verbose
         self.dp = dp
         self.strict_reference = strict_reference

@@ -200,6 +200,19 @@ fltee_status_t ecall_client_size_optimized_secure_aggregation(
                                       blocks created on first use, readout by an oblivious
                                       sort of the tree's slots (n*k accesses instead of
                                       2*n*k + 2*d) */
+#define FLTEE_OPT_PACKED 0x100u    /* d_records is the packed dense layout (below): n rows of
+                                      2 * ceil(d / 2) f32, row c = client c's d values in position
+                                      order, then one ignored f32 when d is odd.  k must equal d and
+                                      d >= 2, else INVALID_PARAMETER.  Implies FLTEE_OPT_DENSE: algs
+                                      3, 4, 5 take the packed accumulate (no scratch; with
+                                      FLTEE_OPT_CLIP the coefficients only) and never set
+                                      FLTEE_DEV_ERR_DENSE_ORDER (there is no index to check).  Every
+                                      other alg, and the tree (FLTEE_OPT_ORAM_TREE / _LAZY), runs as
+                                      it does for (n, d, d) on the records (j, v[j]) unpacked into the
+                                      record scratch (n * d * 8 bytes more of it;
+                                      FLTEE_OPT_CLIP clips that copy in place).  d_records is never
+                                      written.  DP, ACCUMULATE, NO_AVERAGE and n_avg mean what they
+                                      mean on the dense route */
 
 typedef struct fltee_device_opts {
     uint32_t flags;     /* FLTEE_OPT_* */
@@ -218,8 +231,9 @@ typedef struct fltee_device_opts {
 
 /* Aggregate n clients x k records (8 B each: u32 LE idx, f32 LE val),
  * client-major, into d_out[d] (overwritten, or accumulated with
- * FLTEE_OPT_ACCUMULATE).  Returns FLTEE_ERROR_INVALID_PARAMETER for
- * host-detectable argument errors. */
+ * FLTEE_OPT_ACCUMULATE).  With FLTEE_OPT_PACKED d_records is n packed slices
+ * (value-only, 8 * ceil(d / 2) bytes each) instead.  Returns
+ * FLTEE_ERROR_INVALID_PARAMETER for host-detectable argument errors. */
 fltee_status_t fltee_aggregate_device(uint32_t alg, const void *d_records, size_t n, size_t k,
                                       size_t d, float *d_out, const fltee_device_opts *opts,
                                       void *stream);
@@ -264,6 +278,47 @@ fltee_status_t fltee_client_clip_device(void *d_records, size_t n, size_t k, flo
  * 2-byte key layout), bytes_per_client each; the inverse of fltee_decrypt_device. */
 fltee_status_t fltee_encrypt_device(const uint32_t *client_ids, size_t n, const void *d_plain,
                                     size_t bytes_per_client, void *d_cipher, void *stream);
+
+/* ---- packed dense uploads: value-only slices at half the bytes ----------------------------
+ * A dense upload (serialize_dense, k = d) sends client c's slot j as the record (j, v[j]); the
+ * index says nothing.  With U = ceil(d / 2), a PACKED slice is U units of 8 bytes: the d
+ * little-endian f32 values in position order, followed by one f32 of padding when d is odd (the
+ * client writes +0.0, the server ignores it).  A slice stays a whole number of 8-byte units, so
+ * the CTR / GCM kernels, the chunked load and the survivors gather work on "U records per
+ * client" unchanged. */
+/* bytes of one packed slice of d parameters: 8 * ceil(d / 2) */
+size_t fltee_packed_slice_bytes(size_t d);
+/* The packed-call rule, the one place it is decided.  `on`: the switch below; d:
+ * num_of_parameters; k_req: the request's num_of_sparse_parameters; ct_bytes: one client's
+ * ciphertext bytes (without the 16-byte tag under AEAD), or 0 when the payload is not n equal
+ * slices.  Returns 1 when ecall_secure_aggregation reads the payload as packed slices:
+ *     on  &&  d >= 2  &&  k_req in {0, d} (the request declares a dense upload)
+ *         &&  ct_bytes == 8 * ceil(d / 2).
+ * Anything else is read as records exactly as before — a dense 8 * d-byte upload too, so old
+ * and new clients share a server.  d = 1 is never packed (there 8 U == 8 d).  Host arithmetic. */
+int fltee_upload_is_packed(int on, size_t d, size_t k_req, size_t ct_bytes);
+/* Process-wide, like fltee_set_upload_aead; off by default: every call is then read as records,
+ * launch for launch as before.  On: an ecall_secure_aggregation call that the rule above accepts
+ * is loaded, decrypted, verified and (under FLTEE_AEAD_DROP) gathered as U units per client, and
+ * aggregated with FLTEE_OPT_PACKED and k = d: algs 3, 4, 5 by the packed accumulate, algs 1, 2,
+ * 7 and the tree on the unpacked records — [out] bit for bit what the same values sent as
+ * (j, v[j]) records give.  The existing 0x2 refusals come first; advanced's "fold longer than
+ * the payload" refusal counts a packed slice as its d records.  Under AEAD the last AAD word of
+ * a packed call is BE32(aggregation_alg | 0x80000000): a slice sealed as records never verifies
+ * as packed values, nor the other way round (0x3001).  On an eid over several GPUs a packed call
+ * is loaded, verified and unpacked on the root (the dense group path declines it); the
+ * position-range routes (algs 1, 2, 7) shard the unpacked records from there: the one-GPU bits.
+ * ecall_client_size_optimized_secure_aggregation (alg 6) ignores the switch. */
+void fltee_set_upload_packed(int on);
+#define FLTEE_AAD_PACKED_BIT 0x80000000u
+/* [n][2 U] f32 packed slices -> n * d records (j, v[j]), client-major: what every route other
+ * than the packed accumulate runs on.  Asynchronous on `stream`.  d >= 1, d < 2^32. */
+fltee_status_t fltee_unpack_dense_device(const void *d_packed, size_t n, size_t d, void *d_records,
+                                         void *stream);
+/* The client producer: n clients' values [n][d] f32 -> [n][2 U] packed slices (padding +0.0).
+ * Sealing is fltee_encrypt_device / fltee_encrypt_auth_device with 8 U bytes per client. */
+fltee_status_t fltee_client_pack_dense_device(const float *d_values, size_t n, size_t d,
+                                              void *d_packed, void *stream);
 
 /* ---- authenticated uploads: AES-128-GCM (NIST SP 800-38D), 96-bit IV, 128-bit tag ------
  * Per client: K = the session key, H = E_K(0^128), J0 = IV || 0x00000001, keystream block
@@ -337,7 +392,8 @@ fltee_status_t fltee_debug_ghash_window_host(uint32_t client_id, const uint8_t *
  * lib.rs:312-343 and every earlier version of this library.  On: client c's slice is
  * ciphertext (B bytes) || tag (16 bytes) of the scheme above with
  *     IV  = BE32(fl_id) || BE32(round) || BE32(0)
- *     AAD = BE32(fl_id) || BE32(round) || BE32(client_id) || BE32(aggregation_alg),
+ *     AAD = BE32(fl_id) || BE32(round) || BE32(client_id) || BE32(aggregation_alg)
+ * (a packed call, fltee_set_upload_packed: BE32(aggregation_alg | 0x80000000)),
  * so encrypted_parameters_size = n (B + 16) (alg 6 reads client_size (k 8 + 16) bytes) and
  * the records per client are floor(B / 8).  The existing refusals come first and stay 0x2;
  * a slice whose tag does not verify ends the call with *retval = FLTEE_ERROR_MAC_MISMATCH
