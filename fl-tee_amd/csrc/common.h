@@ -169,6 +169,12 @@ hipError_t launch_unpack_dense(const void *packed, size_t n, size_t d, uint64_t 
 hipError_t launch_pack_dense(const float *values, size_t n, size_t d, void *packed, hipStream_t s);
 void set_packed_variant(int v);
 
+// k_trim.hip: the coordinate-wise trimmed mean of n dense uploads (records, or packed rows),
+// t >= 1 clients removed on each side of every output; status: records only
+hipError_t launch_trimmed_mean(const void *in, bool packed, size_t n, size_t d, size_t t, float coef,
+                               float *out, const float *client_coef, bool accumulate, uint32_t *status,
+                               hipStream_t s);
+
 // k_bitonic.hip
 // valid: positions >= valid hold identical pad records (0: unknown); the stage blocks
 // made of pads alone are skipped (exact, data-independent)

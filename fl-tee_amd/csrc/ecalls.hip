@@ -140,6 +140,17 @@ static std::map<uint32_t, AuthReport> g_auth_reports;
 
 // ---- packed dense uploads (fltee_set_upload_packed; k_packed.hip) ---------------------
 static bool g_upload_packed = false;
+// robust aggregation (fltee_set_dense_trim): the per-mille of clients trimmed on each side of
+// every coordinate of a dense call, 0 = off
+static uint32_t g_dense_trim = 0;
+
+// The trim count (include/fltee_agg.h fltee_trim_count): the one place it is decided.
+static size_t trim_count(size_t n, uint32_t per_mille) {
+    if (n == 0) return 0;
+    if (per_mille > 500) per_mille = 500;
+    const size_t t = (size_t)((unsigned __int128)n * per_mille / 1000), cap = (n - 1) / 2;
+    return t < cap ? t : cap;
+}
 
 // The packed-call rule (include/fltee_agg.h fltee_upload_is_packed): the switch is on, the
 // request declares a dense upload of d >= 2 parameters, and every client's ciphertext is
@@ -347,8 +358,9 @@ static bool ecall_takes_tree(uint32_t alg, size_t n, size_t rpc, size_t d) {
 // staged path below).
 // rpc: the records per client the aggregate sees (a packed call: d); packed: c->records holds
 // packed slices (FLTEE_OPT_PACKED)
+// trim: the call's trim count under fltee_set_dense_trim (0: an untrimmed call)
 static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d, size_t k_req,
-                                    size_t batch, uint64_t seed, bool packed = false) {
+                                    size_t batch, uint64_t seed, bool packed = false, size_t trim = 0) {
     fltee_device_opts o;
     std::memset(&o, 0, sizeof o);
     o.k_req = k_req;
@@ -358,6 +370,7 @@ static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d
                       alg == FLTEE_ALG_NON_OBLIVIOUS;
     if (flat && rpc == d) o.flags |= FLTEE_OPT_DENSE;
     if (packed) o.flags |= FLTEE_OPT_PACKED;
+    if (trim) o.flags |= FLTEE_OPT_TRIM, o.trim = trim;
     if (ecall_takes_tree(alg, n, rpc, d)) o.flags |= FLTEE_OPT_ORAM_TREE;
     if (alg == FLTEE_ALG_NIPS19) o.seed = seed ? seed : next_seed();
     // advanced's fold (advanced.rs:66-101) runs once with halo = n: bit for bit for every
@@ -400,8 +413,8 @@ static uint32_t status_to_retval(uint32_t dev_st, uint32_t alg, bool *retry) {
 // rec: the records when they are not c->records (the survivors of a DROP call).
 static uint32_t aggregate_records(DeviceCtx *c, uint32_t alg, size_t n, size_t rpc, size_t d,
                                   size_t k_req, size_t batch, float *d_out, uint64_t seed = 0,
-                                  const void *rec = nullptr, bool packed = false) {
-    fltee_device_opts o = ecall_opts(alg, n, rpc, d, k_req, batch, seed, packed);
+                                  const void *rec = nullptr, bool packed = false, size_t trim = 0) {
+    fltee_device_opts o = ecall_opts(alg, n, rpc, d, k_req, batch, seed, packed, trim);
     if (alg == FLTEE_ALG_OPTIMIZED) o.flags &= ~FLTEE_OPT_K_REQ;
     if (!rec) rec = c->records.ptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -413,6 +426,8 @@ static uint32_t aggregate_records(DeviceCtx *c, uint32_t alg, size_t n, size_t r
         bool retry = false;
         st = status_to_retval(dev_st, alg, &retry);
         if (!retry) return st;
+        // (under fltee_set_dense_trim a sparse rerun would be an untrimmed mean: refused)
+        if (g_dense_trim) return FLTEE_ERROR_INVALID_PARAMETER;
         o.flags &= ~FLTEE_OPT_DENSE;  // the sparse path: exact for any upload
     }
     return FLTEE_ERROR_INVALID_PARAMETER;
@@ -485,7 +500,7 @@ static hipError_t launch_copy_out(const void *src, void *dst, size_t bytes, hipS
 static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, size_t n,
                              const uint8_t *enc, size_t bpc, size_t d, size_t k_req, size_t batch,
                              uint64_t seed, const FLConfig &cfg, float *host_out, float *times,
-                             bool packed = false) {
+                             bool packed = false, size_t trim = 0) {
     const double t0 = now_s();
     const size_t rpc = bpc / 8;                // 8-byte units per client as decrypted
     const size_t rpa = packed ? d : rpc;       // records per client as aggregated
@@ -516,7 +531,7 @@ static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, si
         (!cb && fl_memset_async(d_st, 0, 4, s) != hipSuccess))
         return FLTEE_ERROR_UNEXPECTED;
     fltee_device_opts o = ecall_opts(alg == FLTEE_ALG_OPTIMIZED ? FLTEE_ALG_ADVANCED : alg, n, rpa, d,
-                                     k_req, batch, seed, packed);
+                                     k_req, batch, seed, packed, trim);
     if (alg == FLTEE_ALG_OPTIMIZED) o.flags &= ~FLTEE_OPT_K_REQ;
     // the call's device work: AES (timed by events) -> aggregation (-> DP) -> copy-out
     auto enqueue = [&](bool retry_pass) -> uint32_t {
@@ -529,7 +544,7 @@ static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, si
             return FLTEE_ERROR_UNEXPECTED;
         const uint32_t a = aggregate(alg, c->records.ptr, n, rpa, d, d_out, o, s, d_st);
         if (a != FLTEE_SUCCESS) return a;
-        if (cfg.dp && launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n, next_seed(), s) != hipSuccess)
+        if (cfg.dp && launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n - 2 * trim, next_seed(), s) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
         return launch_copy_out(d_out, c->pin_out.dptr, d4 + 16, s) == hipSuccess
                    ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
@@ -547,6 +562,8 @@ static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, si
         st = status_to_retval(*(const volatile uint32_t *)((const uint8_t *)c->pin_out.ptr + d4), alg,
                               &retry);
         if (!retry) break;
+        // (under fltee_set_dense_trim a sparse rerun would be an untrimmed mean: refused)
+        if (g_dense_trim) return FLTEE_ERROR_INVALID_PARAMETER;
         o.flags &= ~FLTEE_OPT_DENSE;  // the sparse path: exact for any upload
     }
     if (st) return st;
@@ -738,6 +755,16 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     if ((aggregation_alg == FLTEE_ALG_ADVANCED || aggregation_alg == FLTEE_ALG_BUBBLE) &&
         n * num_of_sparse_parameters > n * rpa)
         return fail(FLTEE_ERROR_INVALID_PARAMETER);  // advanced.rs:72 out-of-bounds panic
+    const bool flat = aggregation_alg == FLTEE_ALG_BASELINE || aggregation_alg == FLTEE_ALG_PATH_ORAM ||
+                      aggregation_alg == FLTEE_ALG_NON_OBLIVIOUS;
+    // robust aggregation (fltee_set_dense_trim): only a call that takes the dense or the packed
+    // accumulate can be trimmed; a host that switched trimming on never gets an untrimmed
+    // mean back from any other — the sort-based algs, a sparse upload, the tree, a trim count
+    // past the kernel's lists (evaluated on the request as sent: n' <= n trims no more)
+    const uint32_t trim_pm = g_dense_trim;
+    if (trim_pm && (!flat || !(packed || rpc == d) || (aggregation_alg == FLTEE_ALG_PATH_ORAM && oram_tree_default()) ||
+                    trim_count(n, trim_pm) > FLTEE_TRIM_MAX))
+        return fail(FLTEE_ERROR_INVALID_PARAMETER);
 
     if (!c->outbuf.reserve(d * 4 + 16)) return fail(FLTEE_ERROR_OUT_OF_MEMORY);
     float *d_out = (float *)c->outbuf.ptr;
@@ -764,11 +791,11 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     const bool keepv = keeps_verdict(aead);
     bool verdict_stored = false;
     bool group_tried = false;  // a shape the group declined (or failed on) is not offered to it again
-    const bool flat = aggregation_alg == FLTEE_ALG_BASELINE || aggregation_alg == FLTEE_ALG_PATH_ORAM ||
-                      aggregation_alg == FLTEE_ALG_NON_OBLIVIOUS;
     const bool tree = ecall_takes_tree(aggregation_alg, n, rpa, d);
-    // (a packed call is loaded on the root: the dense group path shards records by column)
-    if (G && flat && !tree && !packed && rpc == d && bpc == d * 8 + tagb) {
+    // (a packed call is loaded on the root: the dense group path shards records by column;
+    // a trimmed call too — it needs every client's value of a column in one place, which a
+    // column shard has, but the group's per-rank sums are untrimmed: the root runs it)
+    if (G && flat && !tree && !packed && !trim_pm && rpc == d && bpc == d * 8 + tagb) {
         // dense uploads over a multi-GPU eid: every GPU loads and decrypts its own
         // parameter range (group.hip); "Loading" = the parallel H2D, "Decryption" = the
         // decrypt + aggregate + gather.  Authenticated: every GPU also hashes its range, the
@@ -825,7 +852,8 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         // one GPU, a small payload: one DMA each way, one host synchronisation (an
         // authenticated upload needs the fail word before the aggregation: the path below)
         st = staged_ecall(c, aggregation_alg, client_ids, n, encrypted_parameters_data, bpc, d, k_req,
-                          0, seed, cfg, updated_parameters_data, execution_time_results, packed);
+                          0, seed, cfg, updated_parameters_data, execution_time_results, packed,
+                          trim_count(n, trim_pm));
         if (st) {
             std::memset(updated_parameters_data, 0, d * sizeof(float));
             std::memset(execution_time_results, 0, 3 * sizeof(float));
@@ -875,10 +903,12 @@ extern "C" fltee_status_t ecall_secure_aggregation(
                 st = group_nips19(G, c, in, n, rpa, k_req, d, seed, coef, d_out);
         }
         if (st == FLTEE_GROUP_FALLBACK)  // one device (or a shape the group does not shard)
-            st = aggregate_records(c, aggregation_alg, n_agg, rpa, d, k_req, 0, d_out, seed, rec, packed);
+            st = aggregate_records(c, aggregation_alg, n_agg, rpa, d, k_req, 0, d_out, seed, rec, packed,
+                                   trim_count(n_agg, trim_pm));
     }
-    if (!st && cfg.dp) {  // lib.rs:399-408
-        if (launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n_agg, next_seed(), c->stream) != hipSuccess)
+    if (!st && cfg.dp) {  // lib.rs:399-408 (a trimmed call: the n' - 2 t clients it averaged)
+        if (launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n_agg - 2 * trim_count(n_agg, trim_pm), next_seed(),
+                            c->stream) != hipSuccess)
             st = FLTEE_ERROR_UNEXPECTED;
     }
     if (!st && fl_memcpy_async(updated_parameters_data, d_out, d * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
@@ -925,6 +955,8 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
     if (uint32_t st = check_uploaded(cfg, client_ids, n)) return fail(st);
     for (size_t i = 0; i < n; ++i)
         if (!g_keys.count(client_ids[i])) return fail(FLTEE_ERROR_UNEXPECTED);
+    // (fltee_set_dense_trim: alg 6 is sort-based and cannot be trimmed — never an untrimmed mean)
+    if (g_dense_trim) return fail(FLTEE_ERROR_INVALID_PARAMETER);
 
     const bool aead = g_upload_aead;
     if (aead && !gcm_sizes_ok(k * 8, 16)) return fail(FLTEE_ERROR_INVALID_PARAMETER);
@@ -1247,6 +1279,13 @@ extern "C" void fltee_set_upload_aead(int on) {
 extern "C" void fltee_set_upload_packed(int on) {
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
     g_upload_packed = on != 0;
+}
+
+extern "C" size_t fltee_trim_count(size_t n, uint32_t per_mille) { return trim_count(n, per_mille); }
+
+extern "C" void fltee_set_dense_trim(uint32_t per_mille) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    g_dense_trim = per_mille > 500 ? 500 : per_mille;
 }
 
 extern "C" int fltee_upload_is_packed(int on, size_t d, size_t k_req, size_t ct_bytes) {

@@ -46,6 +46,8 @@ enum Route : uint32_t {
     kRouteOptimized,     // alg 6: advanced per batch
     kRouteNips19,
     kRoutePacked,        // flat algs, FLTEE_OPT_PACKED: the packed accumulate (k_packed.hip)
+    kRouteTrimDense,     // flat algs, FLTEE_OPT_TRIM with t > 0 on records: the trimmed mean (k_trim.hip)
+    kRouteTrimPacked,    // ... on packed rows
 };
 enum Tail : uint32_t {
     kTailNone,
@@ -160,5 +162,7 @@ hipError_t advanced_batch(const void *rec, size_t n, size_t k, size_t d, size_t 
 hipError_t read_device_word(DeviceCtx *c, const uint32_t *dev_word, size_t *out, hipStream_t s);
 size_t workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o);
 bool reserve(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o);
+// the plan's refusal alone (host arithmetic)
+fltee_status_t plan_status(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o);
 
 }  // namespace fltee

@@ -11,6 +11,7 @@
 
 #include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -240,10 +241,18 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
     const bool packed = (o.flags & FLTEE_OPT_PACKED) != 0;
     const bool dense = packed || (o.flags & FLTEE_OPT_DENSE) != 0;
     const bool tree = alg == FLTEE_ALG_PATH_ORAM && (o.flags & FLTEE_OPT_ORAM_TREE);
+    // the trimmed mean (FLTEE_OPT_TRIM, k_trim.hip): a dense or packed call on the flat algs
+    // without the tree, 2 t < n, t <= FLTEE_TRIM_MAX; t = 0 is the untrimmed route itself
+    const bool trim = (o.flags & FLTEE_OPT_TRIM) != 0;
     const size_t nrec = n * k, k_req = (o.flags & FLTEE_OPT_K_REQ) ? o.k_req : k;
     auto refuse_if = [&p](bool bad) { if (bad) p.status = FLTEE_ERROR_INVALID_PARAMETER; };
     // 32-bit positions; a dense upload has one record per parameter
     refuse_if(n == 0 || nrec + d >= ((size_t)1 << 31) || (dense && k != d) || (packed && d < 2));
+    if (trim) {
+        const bool flat = alg == FLTEE_ALG_BASELINE || alg == FLTEE_ALG_NON_OBLIVIOUS || alg == FLTEE_ALG_PATH_ORAM;
+        refuse_if(!flat || !dense || (o.flags & (FLTEE_OPT_ORAM_TREE | FLTEE_OPT_ORAM_LAZY)) ||
+                  o.trim > FLTEE_TRIM_MAX || 2 * o.trim >= n);
+    }
     switch (alg) {
     case FLTEE_ALG_PATH_ORAM:
     case FLTEE_ALG_BASELINE:
@@ -263,6 +272,7 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
             if (lazy) plan_adv_bytes(p, p.adv = adv_shape(1, p.tree_slots, d, p.tree_slots, 1));
         } else if (dense) {
             p.route = packed ? kRoutePacked : kRouteDense;
+            if (trim && o.trim) p.route = packed ? kRouteTrimPacked : kRouteTrimDense;
         } else if (alg == FLTEE_ALG_NON_OBLIVIOUS && use_scatter_rows(n, k, d)) {
             p.route = kRouteScatterRows;
             p.bytes[kWsMat] = n * d * 4;
@@ -322,12 +332,13 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
         // every route but the dense accumulate (which takes the coefficients) reads records:
         // FLTEE_OPT_DENSE on algs 1, 2, 6, 7 and on the tree only asserts k == d
         p.bytes[kWsCoef] = n * 4;
-        p.clip_records = p.route != kRouteDense && p.route != kRoutePacked;
+        p.clip_records = p.route != kRouteDense && p.route != kRoutePacked && p.route != kRouteTrimDense &&
+                         p.route != kRouteTrimPacked;
         if (p.clip_records) p.bytes[kWsRec] = nrec * 8;
     }
     // every route but the packed accumulate reads records: the plan (n, d, d) has, on the
     // rows unpacked into the record scratch (where FLTEE_OPT_CLIP then clips them in place)
-    p.unpack = packed && p.route != kRoutePacked;
+    p.unpack = packed && p.route != kRoutePacked && p.route != kRouteTrimPacked;
     if (p.unpack) p.bytes[kWsRec] = nrec * 8;
     return p;
 }
@@ -523,7 +534,8 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     if (p.status != FLTEE_SUCCESS) return p.status;
     if (!reserve_plan(c, p, &s)) return FLTEE_ERROR_OUT_OF_MEMORY;
     const bool acc = (o.flags & FLTEE_OPT_ACCUMULATE) != 0;
-    const size_t n_avg = o.n_avg ? o.n_avg : n;
+    // (the trimmed mean averages the n - 2 t clients it keeps; the DP noise takes the same divisor)
+    const size_t n_avg = o.n_avg ? o.n_avg : (o.flags & FLTEE_OPT_TRIM) ? n - 2 * o.trim : n;
     const float coef = (o.flags & FLTEE_OPT_NO_AVERAGE) ? 1.0f : 1.0f / (float)n_avg;
 
     // packed rows off the packed route: every alg below runs on the records (j, v[j])
@@ -537,7 +549,7 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     const float *ccoef = nullptr;
     if (o.flags & FLTEE_OPT_CLIP) {
         float *cf = (float *)c->ws_coef.ptr;
-        if ((p.route == kRoutePacked ? launch_packed_clip_coef(rec, n, d, o.clipping, cf, s)
+        if ((p.route == kRoutePacked || p.route == kRouteTrimPacked ? launch_packed_clip_coef(rec, n, d, o.clipping, cf, s)
                                      : launch_client_clip_coef(rec, n, k, o.clipping, cf, s)) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
         ccoef = cf;
@@ -572,6 +584,10 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
         break;
     case kRoutePacked:
         e = launch_dense_accumulate_packed(rec, n, d, coef, out, ccoef, acc, s);
+        break;
+    case kRouteTrimDense:
+    case kRouteTrimPacked:
+        e = launch_trimmed_mean(rec, p.route == kRouteTrimPacked, n, d, o.trim, coef, out, ccoef, acc, status, s);
         break;
     case kRouteScatterRows:
         if (c->mat_clean_ptr != c->ws_mat.ptr || c->mat_clean_cap != c->ws_mat.cap) {
@@ -655,6 +671,10 @@ size_t workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d, const fltee_d
     return sum;
 }
 
+fltee_status_t plan_status(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
+    return plan_for(alg, n, k, d, o).status;
+}
+
 bool reserve(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
     DeviceCtx *c = current_ctx();
     return c && reserve_plan(c, plan_for(alg, n, k, d, o), nullptr);
@@ -693,11 +713,22 @@ static fltee_device_opts default_opts() {
     return o;
 }
 
+// The caller's options.  `trim`, the struct's last field, is read only under FLTEE_OPT_TRIM:
+// a caller built against the struct that ended at d_status never sets the flag, and nothing
+// past its struct is touched.
+static fltee_device_opts read_opts(const fltee_device_opts *opts) {
+    fltee_device_opts o = default_opts();
+    if (!opts) return o;
+    std::memcpy(&o, opts, offsetof(fltee_device_opts, trim));
+    if (o.flags & FLTEE_OPT_TRIM) o.trim = opts->trim;
+    return o;
+}
+
 extern "C" fltee_status_t fltee_aggregate_device(uint32_t alg, const void *d_records, size_t n,
                                                  size_t k, size_t d, float *d_out,
                                                  const fltee_device_opts *opts, void *stream) {
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
-    const fltee_device_opts o = opts ? *opts : default_opts();
+    const fltee_device_opts o = read_opts(opts);
     DeviceCtx *c = current_ctx();
     if (!c) return FLTEE_ERROR_UNEXPECTED;
     uint32_t *status = o.d_status ? o.d_status : c->status;
@@ -708,14 +739,17 @@ extern "C" fltee_status_t fltee_aggregate_device(uint32_t alg, const void *d_rec
 
 extern "C" size_t fltee_workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d,
                                         const fltee_device_opts *opts) {
-    const fltee_device_opts o = opts ? *opts : default_opts();
+    const fltee_device_opts o = read_opts(opts);
     return workspace_bytes(alg, n, k, d, o);
 }
 
 extern "C" fltee_status_t fltee_reserve(uint32_t alg, size_t n, size_t k, size_t d,
                                         const fltee_device_opts *opts) {
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
-    const fltee_device_opts o = opts ? *opts : default_opts();
+    const fltee_device_opts o = read_opts(opts);
+    // a refused trimmed call is refused here too, by the plan, before anything is reserved
+    if ((o.flags & FLTEE_OPT_TRIM) && plan_status(alg, n, k, d, o) != FLTEE_SUCCESS)
+        return FLTEE_ERROR_INVALID_PARAMETER;
     return reserve(alg, n, k, d, o) ? FLTEE_SUCCESS : FLTEE_ERROR_OUT_OF_MEMORY;
 }
 
@@ -1218,7 +1252,7 @@ extern "C" void fltee_debug_set_fused_init(int on) { fltee::set_fused_init(on); 
 // device.  The sizes are filled in for a refused shape too.
 extern "C" fltee_status_t fltee_debug_plan(uint32_t alg, size_t n, size_t k, size_t d,
                                            const fltee_device_opts *opts, uint64_t *out) {
-    return fltee::debug_plan_words(alg, n, k, d, opts ? *opts : default_opts(), out);
+    return fltee::debug_plan_words(alg, n, k, d, read_opts(opts), out);
 }
 // test hooks: which engine scratch buffers grew (allocated) since the last call — bit w for
 // buffer w in Ws order — read and cleared; and the current device's engine scratch released

@@ -47,6 +47,8 @@ OPT_K_REQ = 0x20
 OPT_ORAM_TREE = 0x40
 OPT_ORAM_LAZY = 0x80
 OPT_PACKED = 0x100  # d_records: packed dense slices (value-only rows of 2 * ceil(d / 2) f32)
+OPT_TRIM = 0x200  # coordinate-wise trimmed mean of a dense call, DeviceOpts.trim clients a side
+TRIM_MAX = 64  # FLTEE_TRIM_MAX
 AAD_PACKED_BIT = 0x80000000  # FLTEE_AAD_PACKED_BIT: a packed call's last AAD word is alg | this
 
 
@@ -62,6 +64,7 @@ class DeviceOpts(ctypes.Structure):
         ("n_avg", ctypes.c_size_t),
         ("fold_halo", ctypes.c_size_t),
         ("d_status", ctypes.c_void_p),
+        ("trim", ctypes.c_size_t),
     ]
 
 
@@ -94,6 +97,8 @@ SIGNATURES = {
     "fltee_set_upload_packed": (None, [ctypes.c_int]),
     "fltee_unpack_dense_device": (_U32, [_P, _S, _S, _P, _P]),
     "fltee_client_pack_dense_device": (_U32, [_P, _S, _S, _P, _P]),
+    "fltee_trim_count": (_S, [_S, _U32]),
+    "fltee_set_dense_trim": (None, [_U32]),
     "fltee_set_upload_aead": (None, [ctypes.c_int]),
     "fltee_set_upload_aead_policy": (None, [ctypes.c_int, _S]),
     "fltee_auth_report": (_U32, [_U64, _U32, _P, _P, _S, _P]),

@@ -104,6 +104,10 @@ class Enclave:
             _p(times))
         return st, rv.value, out, times
 
+    def set_dense_trim(self, per_mille):
+        """fltee_set_dense_trim (process-wide; see the module function of the same name)."""
+        set_dense_trim(per_mille)
+
     def auth_report(self, fl_id):
         """fltee_auth_report: (round, [failed client ids in upload order]) of fl_id's last
         authenticated ECALL under the "report" / "drop" policies; an empty list after a clean
@@ -152,6 +156,23 @@ def set_upload_packed(on):
     produce_payloads(packed=True)): half the bytes, the same [out] bit for bit.  Every other
     call — a dense 8 * d-byte upload too — is read as records, as before."""
     L.lib().fltee_set_upload_packed(1 if on else 0)
+
+
+def set_dense_trim(per_mille):
+    """Robust aggregation (fltee_set_dense_trim; 0, the default, is off): while on, a dense or
+    packed ecall_secure_aggregation call on algs 3, 4, 5 returns the coordinate-wise trimmed mean
+    — per coordinate the t = trim_count(n', per_mille) smallest and the t largest client values
+    are removed (a NaN is always an extreme) and the rest averaged over n' - 2 t; 500 asks for
+    the median.  Every call that cannot be trimmed (algs 1, 2, 6, 7, a sparse upload, the tree)
+    ends with retval 0x2, never with an untrimmed mean."""
+    if not 0 <= int(per_mille) <= 500:
+        raise ValueError(f"trim per mille {per_mille!r} is not in 0..500")
+    L.lib().fltee_set_dense_trim(int(per_mille))
+
+
+def trim_count(n, per_mille):
+    """fltee_trim_count: min(n * per_mille // 1000, (n - 1) // 2) clients trimmed on each side."""
+    return int(L.lib().fltee_trim_count(n, per_mille))
 
 
 def upload_is_packed(on, d, k_req, ct_bytes):

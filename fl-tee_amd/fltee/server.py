@@ -23,20 +23,38 @@ request).  Documented deviations from the reference host:
     dense upload and carries 8 * ceil(d / 2) bytes per client (value-only slices,
     fltee.client.pack_dense) is aggregated from half the bytes, with the same reply; every
     other request, a dense 8 * d-byte one too, is answered as before.
+  * `trim_per_mille=N` (0, off, by default; 0..500) answers dense uploads to algs 3, 4, 5 with
+    the coordinate-wise trimmed mean: per coordinate the N per mille smallest and largest
+    client values are removed (500: the median), so a client sealing 1e30 or NaN no longer
+    owns the round.  Every request that cannot be trimmed (another alg, a sparse upload) is a
+    ServerPanic (retval 0x2), never an untrimmed mean.
 """
+import argparse
 import time
 
 from . import _lib as L
-from .ecalls import AEAD_POLICIES, Enclave, set_upload_aead, set_upload_aead_policy, set_upload_packed
+from .ecalls import (AEAD_POLICIES, Enclave, set_dense_trim, set_upload_aead, set_upload_aead_policy,
+                     set_upload_packed)
 
 
 class ServerPanic(RuntimeError):
     pass
 
 
+def per_mille(text):
+    """argparse type of --trim-per-mille: an integer in 0..500"""
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not an integer")
+    if not 0 <= v <= 500:
+        raise argparse.ArgumentTypeError(f"{v} is not in 0..500")
+    return v
+
+
 class Aggregator:
     def __init__(self, device=0, verbose=False, dp=False, strict_reference=False, enclave=None,
-                 aead=False, aead_policy="abort", min_survivors=1, packed=False):
+                 aead=False, aead_policy="abort", min_survivors=1, packed=False, trim_per_mille=0):
         if aead_policy not in AEAD_POLICIES:
             raise ValueError(f"aead_policy must be one of {sorted(AEAD_POLICIES)}")
         if aead_policy != "abort" and not aead:
@@ -51,6 +69,11 @@ class Aggregator:
         self.packed = bool(packed)
         if self.packed:  # process-wide too
             set_upload_packed(True)
+        self.trim_per_mille = int(trim_per_mille)
+        if not 0 <= self.trim_per_mille <= 500:
+            raise ValueError("trim_per_mille must be in 0..500")
+        if self.trim_per_mille:  # process-wide too
+            set_dense_trim(self.trim_per_mille)
         self.verbose = verbose
         self.dp = dp
         self.strict_reference = strict_reference

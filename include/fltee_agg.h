@@ -213,6 +213,34 @@ fltee_status_t ecall_client_size_optimized_secure_aggregation(
                                       FLTEE_OPT_CLIP clips that copy in place).  d_records is never
                                       written.  DP, ACCUMULATE, NO_AVERAGE and n_avg mean what they
                                       mean on the dense route */
+#define FLTEE_OPT_TRIM 0x200u      /* coordinate-wise trimmed mean of a dense call (k_trim.hip):
+                                      algs 3, 4, 5 with FLTEE_OPT_DENSE or FLTEE_OPT_PACKED, k = d,
+                                      t = opts.trim.  Per output j, with x_c client c's value at j
+                                      (FLTEE_OPT_CLIP: v * coef_c rounded, as the dense routes apply
+                                      it) and ord(x) = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000) on
+                                      b = bits(x) — a total order on every bit pattern, -NaN < -inf
+                                      < ... < -0.0 < +0.0 < ... < +inf < +NaN, so a NaN is always an
+                                      extreme and the first value trimmed: the t clients smallest by
+                                      (ord ascending, c ascending) are removed, then, of the rest,
+                                      the t clients largest by (ord descending, c ascending) —
+                                      among equal bit patterns the earliest uploads go first on
+                                      both sides.  out[j] = sum * (1f32 / (f32)div), sum = the
+                                      in-order f32 sum ((+0.0 + x_c1) + x_c2) + ... of the kept
+                                      clients, div = n_avg ? n_avg : n - 2 t, which is the DP
+                                      noise's divisor too; ACCUMULATE, NO_AVERAGE and DP mean what
+                                      they mean on the dense route.  t = 0 is the untrimmed dense
+                                      result bit for bit (the dense / packed accumulate runs); odd
+                                      n with t = (n - 1) / 2 is the median, even n with
+                                      t = n / 2 - 1 the mean of the two middle values.  Oblivious:
+                                      every value is read at a fixed address (twice), the launch
+                                      shapes depend on (n, d, t) and the pointers' alignment, all
+                                      public.  No scratch (with FLTEE_OPT_CLIP the coefficients
+                                      only); the records layout raises FLTEE_DEV_ERR_DENSE_ORDER as
+                                      the dense route does.  Refused with INVALID_PARAMETER by host
+                                      arithmetic, before anything is reserved or launched:
+                                      trim > FLTEE_TRIM_MAX, 2 * trim >= n, any other alg, a call
+                                      that is not dense, FLTEE_OPT_ORAM_TREE / _LAZY */
+#define FLTEE_TRIM_MAX 64
 
 typedef struct fltee_device_opts {
     uint32_t flags;     /* FLTEE_OPT_* */
@@ -227,6 +255,9 @@ typedef struct fltee_device_opts {
                            indices distinct) bit for bit, longer ones re-associated at the
                            fold's walk boundaries */
     uint32_t *d_status; /* optional device status word (never cleared by the library) */
+    size_t trim;        /* FLTEE_OPT_TRIM: clients removed on each side of every coordinate.  The
+                           last field, read only when the flag is set: a caller built against the
+                           struct without it, which never sets the flag, is unaffected */
 } fltee_device_opts;
 
 /* Aggregate n clients x k records (8 B each: u32 LE idx, f32 LE val),
@@ -319,6 +350,32 @@ fltee_status_t fltee_unpack_dense_device(const void *d_packed, size_t n, size_t 
  * Sealing is fltee_encrypt_device / fltee_encrypt_auth_device with 8 U bytes per client. */
 fltee_status_t fltee_client_pack_dense_device(const float *d_values, size_t n, size_t d,
                                               void *d_packed, void *stream);
+
+/* ---- robust aggregation: the coordinate-wise trimmed mean / median behind the ECALL ----------
+ * A client with a valid session key can seal an authentic slice of 1e30 or NaN; a plain mean
+ * hands it the round, and the host cannot repair that afterwards (it never sees the updates).
+ * The trim count, the one place it is decided (host arithmetic):
+ *     t = min(n * per_mille / 1000, (n - 1) / 2)   in integers, per_mille <= 500 (above: 500),
+ * 0 for n = 0.  per_mille = 500 asks for the median (odd n; even n: the two middle values). */
+size_t fltee_trim_count(size_t n, uint32_t per_mille);
+/* Process-wide, like fltee_set_upload_packed; 0 (default) is off: every call is then launch for
+ * launch what it was.  A value above 500 is stored as 500.  On: ecall_secure_aggregation computes
+ * t = fltee_trim_count(n', per_mille), n' = the clients actually aggregated (the survivors under
+ * FLTEE_AEAD_DROP: the gather, the trim and the divisor n' - 2 t agree), and a call on the dense
+ * or the packed route (algs 3, 4, 5 on a dense upload in position; the staged and the pipelined
+ * path alike) is aggregated with FLTEE_OPT_TRIM: [out] = the kept clients' in-order sum times
+ * 1f32 / (f32)(n' - 2 t), the DP noise divided by n' - 2 t.  t = 0 (n' <= 2, a tiny per_mille)
+ * runs untrimmed.  A host that switched trimming on never gets a silently untrimmed mean back:
+ * what cannot be trimmed ends with 0x2, with the existing 0x2 refusals ([out] zero-filled, the
+ * timers written, the round kept) — algs 1, 2 and 7, a sparse upload to algs 3, 4, 5, alg 5 under
+ * fltee_set_path_oram_tree(1), t > FLTEE_TRIM_MAX, and every
+ * ecall_client_size_optimized_secure_aggregation call; a dense-sized records upload out of
+ * position (FLTEE_DEV_ERR_DENSE_ORDER, rerun sparse otherwise) ends with 0x2 after the one status
+ * readback there already is.  Under AEAD the verification and the verdict come first, unchanged.
+ * On an eid over several GPUs the dense group path declines a trimmed call and the root runs
+ * it: the one-GPU bits.  Nothing new is revealed: the launch shapes depend on (n', d, t) and
+ * the buffers' alignment, all public. */
+void fltee_set_dense_trim(uint32_t per_mille);
 
 /* ---- authenticated uploads: AES-128-GCM (NIST SP 800-38D), 96-bit IV, 128-bit tag ------
  * Per client: K = the session key, H = E_K(0^128), J0 = IV || 0x00000001, keystream block
