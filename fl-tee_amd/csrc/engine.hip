@@ -415,6 +415,31 @@ hipError_t ordered_from_list(DeviceCtx *c, const uint64_t *sel, size_t lc, size_
     return ordered_fold_records(c, sel, lc, d, coef, out, acc, status, s);
 }
 
+// fltee_debug_sort_records_device: the ordered fold's sort alone, on scratch reserved as
+// ordered_from_list reserves it — the counting sort, no output to zero-fill; or,
+// fltee_debug_set_radix_order(0), the composite-key network's order — then the n sorted
+// records copied out of ws_keys.
+static hipError_t debug_sort_records(DeviceCtx *c, const void *rec, size_t n, size_t d, void *dst,
+                                     uint32_t *status, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (!c->ws_keys.reserve(n * 8) || !c->ws_radix.reserve(ordered_radix_bytes(n, d, false)))
+        return hipErrorOutOfMemory;
+    uint64_t *sorted = (uint64_t *)c->ws_keys.ptr;
+    hipError_t e;
+    if (g_radix_order) {
+        e = launch_sort_records_by_idx(rec, n, d, c->ws_radix.ptr, c->ws_radix.cap, sorted, status,
+                                       nullptr, 0, s);
+    } else {
+        const size_t mc = next_pow2_sz(n);
+        uint64_t *keys = (uint64_t *)c->ws_radix.ptr;
+        e = launch_composite_init(rec, n, d, mc, keys, status, s);
+        if (e == hipSuccess) e = bitonic_sort(keys, mc, 1, 0, s, n);
+        if (e == hipSuccess) e = launch_gather_by_keys(keys, n, rec, sorted, s);
+    }
+    if (e == hipSuccess) e = fl_memcpy_async(dst, sorted, n * 8, hipMemcpyDeviceToDevice, s);
+    return e;
+}
+
 hipError_t read_device_word(DeviceCtx *c, const uint32_t *dev_word, size_t *out, hipStream_t s) {
     if (!c->host_word && hipHostMalloc((void **)&c->host_word, 64, hipHostMallocDefault) != hipSuccess) {
         c->host_word = nullptr;
@@ -1059,6 +1084,18 @@ extern "C" fltee_status_t fltee_ordered_list_device(const void *d_list, size_t l
     if (d == 0) return FLTEE_SUCCESS;
     return ordered_from_list(c, (const uint64_t *)d_list, lc, d, coef, d_out, false, c->status,
                              (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
+// test hook: the ordered fold's stable sort by min(idx, d) alone (fltee_agg.h)
+extern "C" fltee_status_t fltee_debug_sort_records_device(const void *d_rec, size_t n, size_t d,
+                                                          void *d_sorted, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    DeviceCtx *c = current_ctx();
+    if (!c || d == 0 || n >= ((size_t)1 << 29) || (n && (!d_rec || !d_sorted)))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    return debug_sort_records(c, d_rec, n, d, d_sorted, c->status, (hipStream_t)stream) == hipSuccess
                ? FLTEE_SUCCESS
                : FLTEE_ERROR_UNEXPECTED;
 }

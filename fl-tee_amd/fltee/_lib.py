@@ -135,6 +135,7 @@ SIGNATURES = {
     "fltee_safe_aggregate_device": (_U32, [_P, _S, _S, _P, _P]),
     "fltee_select_device": (_U32, [_P, _S, _S, _P, _S, _P, _P]),
     "fltee_ordered_list_device": (_U32, [_P, _S, _S, _F, _P, _P]),
+    "fltee_debug_sort_records_device": (_U32, [_P, _S, _S, _P, _P]),
     "fltee_debug_set_seed": (None, [_U64]),
     "fltee_set_path_oram_tree": (None, [ctypes.c_int]),
     "fltee_set_advanced_exact_runs": (None, [ctypes.c_int]),

@@ -473,3 +473,14 @@ def ordered_list(lst, d, coef, out=None, stream=None):
                                              _stream(stream)),
            "fltee_ordered_list_device")
     return out
+
+
+def debug_sort_records(records, d, out=None, stream=None):
+    """The ordered fold's stable sort alone (fltee_debug_sort_records_device): the records in
+    order of min(idx, d), upload order within an index, as a new int64 tensor."""
+    if out is None:
+        out = torch.empty_like(records)
+    _check(L.lib().fltee_debug_sort_records_device(_ptr(records), records.numel(), d, _ptr(out),
+                                                   _stream(stream)),
+           "fltee_debug_sort_records_device")
+    return out

@@ -682,6 +682,12 @@ fltee_status_t fltee_select_device(const void *d_src, size_t m, size_t d, void *
                                    size_t cap, size_t *count, void *stream);
 fltee_status_t fltee_ordered_list_device(const void *d_list, size_t lc, size_t d, float coef,
                                          float *d_out, void *stream);
+/* Test hook: the stable sort that fold runs, alone: the n 8-byte records of d_rec in
+ * order of min(idx, d), upload order within an index (the records with idx >= d last,
+ * and FLTEE_DEV_ERR_INDEX_RANGE in the library's status word), into d_sorted (another
+ * buffer of n records).  n < 2^29, d >= 1. */
+fltee_status_t fltee_debug_sort_records_device(const void *d_rec, size_t n, size_t d,
+                                               void *d_sorted, void *stream);
 
 /* Test hooks: deterministic RNG seed for sampling / nips19 / DP (0 = off). */
 /* The ECALLs' path_oram (aggregation_alg 5): on = the tree Path ORAM of oram.rs:64-118
