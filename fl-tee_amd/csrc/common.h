@@ -169,6 +169,17 @@ hipError_t launch_unpack_dense(const void *packed, size_t n, size_t d, uint64_t 
 hipError_t launch_pack_dense(const float *values, size_t n, size_t d, void *packed, hipStream_t s);
 void set_packed_variant(int v);
 
+// k_bf16.hip: bf16 dense slices — n rows of 4 * ceil(d / 4) bf16: a client's d values in
+// position order, then ignored padding; widened exactly (bits << 16).  The four launchers
+// are their packed siblings' contracts on these rows (pack narrows f32 to bf16, round to
+// nearest even in integer ops).
+hipError_t launch_dense_accumulate_bf16(const void *rows, size_t n, size_t d, float coef, float *out,
+                                        const float *client_coef, bool accumulate, hipStream_t s);
+hipError_t launch_bf16_clip_coef(const void *rows, size_t n, size_t d, float clipping, float *coef,
+                                 hipStream_t s);
+hipError_t launch_unpack_bf16(const void *rows, size_t n, size_t d, uint64_t *rec, hipStream_t s);
+hipError_t launch_pack_bf16(const float *values, size_t n, size_t d, void *rows, hipStream_t s);
+
 // k_trim.hip: the coordinate-wise trimmed mean of n dense uploads (records, or packed rows),
 // t >= 1 clients removed on each side of every output; status: records only
 hipError_t launch_trimmed_mean(const void *in, bool packed, size_t n, size_t d, size_t t, float coef,

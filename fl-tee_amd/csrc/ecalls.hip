@@ -160,6 +160,17 @@ static bool upload_is_packed(bool on, size_t d, size_t k_req, size_t ct_bytes) {
     return on && d >= 2 && (k_req == 0 || k_req == d) && ct_bytes / 8 == (d + 1) / 2 && ct_bytes % 8 == 0;
 }
 
+// ---- bf16 dense uploads (fltee_set_upload_bf16; k_bf16.hip) ---------------------------
+static bool g_upload_bf16 = false;
+
+// The bf16-call rule (include/fltee_agg.h fltee_upload_is_bf16): the packed rule on a slice of
+// 8 * ceil(d / 4) bytes.  d >= 3: below that a bf16 slice has the size of a packed slice
+// (d = 2) or of a record (d = 1); from there the three sizes differ, so one server answers
+// all three formats.
+static bool upload_is_bf16(bool on, size_t d, size_t k_req, size_t ct_bytes) {
+    return on && d >= 3 && (k_req == 0 || k_req == d) && ct_bytes / 8 == (d + 3) / 4 && ct_bytes % 8 == 0;
+}
+
 static bool keeps_verdict(bool aead) { return aead && g_aead_policy != FLTEE_AEAD_ABORT; }
 
 // fail: the n fail words as load_and_decrypt read them back (the word gathering them behind)
@@ -188,7 +199,8 @@ static inline void put_be32(uint8_t *p, uint32_t v) {
 
 // What the ECALLs bind: IV = BE32(fl_id) || BE32(round) || BE32(0), AAD = BE32(fl_id) ||
 // BE32(round) || BE32(client_id) || BE32(aggregation_alg) — alg: a packed call passes
-// aggregation_alg | FLTEE_AAD_PACKED_BIT, so a slice sealed for one format fails under the other
+// aggregation_alg | FLTEE_AAD_PACKED_BIT, a bf16 call aggregation_alg | FLTEE_AAD_BF16_BIT, so a
+// slice sealed for one format fails under the others
 static void ecall_gcm_args(uint32_t fl_id, uint32_t round, const uint32_t *ids, size_t n,
                            uint32_t alg, GcmArgs &g) {
     put_be32(g.iv, fl_id);
@@ -356,11 +368,11 @@ static bool ecall_takes_tree(uint32_t alg, size_t n, size_t rpc, size_t d) {
 
 // The options aggregate_records gives aggregate() for an ECALL's alg (shared with the
 // staged path below).
-// rpc: the records per client the aggregate sees (a packed call: d); packed: c->records holds
-// packed slices (FLTEE_OPT_PACKED)
+// rpc: the records per client the aggregate sees (a packed or bf16 call: d); fmt: c->records
+// holds value-only slices — FLTEE_OPT_PACKED or FLTEE_OPT_BF16, 0 for records
 // trim: the call's trim count under fltee_set_dense_trim (0: an untrimmed call)
 static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d, size_t k_req,
-                                    size_t batch, uint64_t seed, bool packed = false, size_t trim = 0) {
+                                    size_t batch, uint64_t seed, uint32_t fmt = 0, size_t trim = 0) {
     fltee_device_opts o;
     std::memset(&o, 0, sizeof o);
     o.k_req = k_req;
@@ -369,7 +381,7 @@ static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d
     const bool flat = alg == FLTEE_ALG_BASELINE || alg == FLTEE_ALG_PATH_ORAM ||
                       alg == FLTEE_ALG_NON_OBLIVIOUS;
     if (flat && rpc == d) o.flags |= FLTEE_OPT_DENSE;
-    if (packed) o.flags |= FLTEE_OPT_PACKED;
+    o.flags |= fmt;
     if (trim) o.flags |= FLTEE_OPT_TRIM, o.trim = trim;
     if (ecall_takes_tree(alg, n, rpc, d)) o.flags |= FLTEE_OPT_ORAM_TREE;
     if (alg == FLTEE_ALG_NIPS19) o.seed = seed ? seed : next_seed();
@@ -413,8 +425,8 @@ static uint32_t status_to_retval(uint32_t dev_st, uint32_t alg, bool *retry) {
 // rec: the records when they are not c->records (the survivors of a DROP call).
 static uint32_t aggregate_records(DeviceCtx *c, uint32_t alg, size_t n, size_t rpc, size_t d,
                                   size_t k_req, size_t batch, float *d_out, uint64_t seed = 0,
-                                  const void *rec = nullptr, bool packed = false, size_t trim = 0) {
-    fltee_device_opts o = ecall_opts(alg, n, rpc, d, k_req, batch, seed, packed, trim);
+                                  const void *rec = nullptr, uint32_t fmt = 0, size_t trim = 0) {
+    fltee_device_opts o = ecall_opts(alg, n, rpc, d, k_req, batch, seed, fmt, trim);
     if (alg == FLTEE_ALG_OPTIMIZED) o.flags &= ~FLTEE_OPT_K_REQ;
     if (!rec) rec = c->records.ptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -500,10 +512,10 @@ static hipError_t launch_copy_out(const void *src, void *dst, size_t bytes, hipS
 static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, size_t n,
                              const uint8_t *enc, size_t bpc, size_t d, size_t k_req, size_t batch,
                              uint64_t seed, const FLConfig &cfg, float *host_out, float *times,
-                             bool packed = false, size_t trim = 0) {
+                             uint32_t fmt = 0, size_t trim = 0) {
     const double t0 = now_s();
     const size_t rpc = bpc / 8;                // 8-byte units per client as decrypted
-    const size_t rpa = packed ? d : rpc;       // records per client as aggregated
+    const size_t rpa = fmt ? d : rpc;          // records per client as aggregated
     const size_t rkb = (n * 44 * 4 + 15) / 16 * 16, cb = n * bpc;
     const size_t d4 = (d * 4 + 15) / 16 * 16;
     const bool zero_copy = 16 + rkb + cb <= kZeroCopyBytes;
@@ -531,7 +543,7 @@ static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, si
         (!cb && fl_memset_async(d_st, 0, 4, s) != hipSuccess))
         return FLTEE_ERROR_UNEXPECTED;
     fltee_device_opts o = ecall_opts(alg == FLTEE_ALG_OPTIMIZED ? FLTEE_ALG_ADVANCED : alg, n, rpa, d,
-                                     k_req, batch, seed, packed, trim);
+                                     k_req, batch, seed, fmt, trim);
     if (alg == FLTEE_ALG_OPTIMIZED) o.flags &= ~FLTEE_OPT_K_REQ;
     // the call's device work: AES (timed by events) -> aggregation (-> DP) -> copy-out
     auto enqueue = [&](bool retry_pass) -> uint32_t {
@@ -747,22 +759,29 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     // as rpc = ceil(d / 2) 8-byte units per client, aggregated as rpa = d records
     const bool packed = upload_is_packed(g_upload_packed, d, num_of_sparse_parameters,
                                          encrypted_parameters_size % n ? 0 : ctb);
+    // bf16 dense slices (fltee_set_upload_bf16) likewise: rpc = ceil(d / 4) units per client
+    // (for d >= 3 no size is both a packed and a bf16 slice)
+    const bool bf16 = !packed && upload_is_bf16(g_upload_bf16, d, num_of_sparse_parameters,
+                                                encrypted_parameters_size % n ? 0 : ctb);
+    const uint32_t fmt = packed ? FLTEE_OPT_PACKED : bf16 ? FLTEE_OPT_BF16 : 0u;
     const size_t rpc = ctb / 8;
-    const size_t rpa = packed ? d : rpc;
+    const size_t rpa = fmt ? d : rpc;
     GcmArgs gcm;
     if (aead)
-        ecall_gcm_args(fl_id, round, client_ids, n, aggregation_alg | (packed ? FLTEE_AAD_PACKED_BIT : 0u), gcm);
+        ecall_gcm_args(fl_id, round, client_ids, n,
+                       aggregation_alg | (packed ? FLTEE_AAD_PACKED_BIT : bf16 ? FLTEE_AAD_BF16_BIT : 0u), gcm);
     if ((aggregation_alg == FLTEE_ALG_ADVANCED || aggregation_alg == FLTEE_ALG_BUBBLE) &&
         n * num_of_sparse_parameters > n * rpa)
         return fail(FLTEE_ERROR_INVALID_PARAMETER);  // advanced.rs:72 out-of-bounds panic
     const bool flat = aggregation_alg == FLTEE_ALG_BASELINE || aggregation_alg == FLTEE_ALG_PATH_ORAM ||
                       aggregation_alg == FLTEE_ALG_NON_OBLIVIOUS;
     // robust aggregation (fltee_set_dense_trim): only a call that takes the dense or the packed
-    // accumulate can be trimmed; a host that switched trimming on never gets an untrimmed
+    // accumulate can be trimmed (a bf16 call: the records trim on its unpacked copy); a host
+    // that switched trimming on never gets an untrimmed
     // mean back from any other — the sort-based algs, a sparse upload, the tree, a trim count
     // past the kernel's lists (evaluated on the request as sent: n' <= n trims no more)
     const uint32_t trim_pm = g_dense_trim;
-    if (trim_pm && (!flat || !(packed || rpc == d) || (aggregation_alg == FLTEE_ALG_PATH_ORAM && oram_tree_default()) ||
+    if (trim_pm && (!flat || !(fmt || rpc == d) || (aggregation_alg == FLTEE_ALG_PATH_ORAM && oram_tree_default()) ||
                     trim_count(n, trim_pm) > FLTEE_TRIM_MAX))
         return fail(FLTEE_ERROR_INVALID_PARAMETER);
 
@@ -792,10 +811,10 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     bool verdict_stored = false;
     bool group_tried = false;  // a shape the group declined (or failed on) is not offered to it again
     const bool tree = ecall_takes_tree(aggregation_alg, n, rpa, d);
-    // (a packed call is loaded on the root: the dense group path shards records by column;
+    // (a packed or bf16 call is loaded on the root: the dense group path shards records by column;
     // a trimmed call too — it needs every client's value of a column in one place, which a
     // column shard has, but the group's per-rank sums are untrimmed: the root runs it)
-    if (G && flat && !tree && !packed && !trim_pm && rpc == d && bpc == d * 8 + tagb) {
+    if (G && flat && !tree && !fmt && !trim_pm && rpc == d && bpc == d * 8 + tagb) {
         // dense uploads over a multi-GPU eid: every GPU loads and decrypts its own
         // parameter range (group.hip); "Loading" = the parallel H2D, "Decryption" = the
         // decrypt + aggregate + gather.  Authenticated: every GPU also hashes its range, the
@@ -816,10 +835,12 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     }
     // (the exact-runs policy folds on one GPU: one sequential walk of the sorted array)
     // (alg 7, once the host has opted in, shards like advanced: the same fold and tail)
-    const bool sharded = G && (((aggregation_alg == FLTEE_ALG_ADVANCED ||
+    // (a bf16 call is not sharded: the root runs it whole, the one-GPU bits)
+    const bool sharded = G && !bf16 &&
+                         (((aggregation_alg == FLTEE_ALG_ADVANCED ||
                                  (aggregation_alg == FLTEE_ALG_BUBBLE && bubble_ecall_default())) &&
-                                k_req == rpa && !exact_runs_default()) ||
-                               aggregation_alg == FLTEE_ALG_NIPS19);
+                           k_req == rpa && !exact_runs_default()) ||
+                          aggregation_alg == FLTEE_ALG_NIPS19);
     // nips19 draws its seed (Laplace counts, shuffle key) once per call, whichever path
     // runs it, so a multi-GPU eid consumes the seed sequence exactly as one GPU does
     const uint64_t seed = aggregation_alg == FLTEE_ALG_NIPS19 ? next_seed() : 0;
@@ -852,7 +873,7 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         // one GPU, a small payload: one DMA each way, one host synchronisation (an
         // authenticated upload needs the fail word before the aggregation: the path below)
         st = staged_ecall(c, aggregation_alg, client_ids, n, encrypted_parameters_data, bpc, d, k_req,
-                          0, seed, cfg, updated_parameters_data, execution_time_results, packed,
+                          0, seed, cfg, updated_parameters_data, execution_time_results, fmt,
                           trim_count(n, trim_pm));
         if (st) {
             std::memset(updated_parameters_data, 0, d * sizeof(float));
@@ -903,7 +924,7 @@ extern "C" fltee_status_t ecall_secure_aggregation(
                 st = group_nips19(G, c, in, n, rpa, k_req, d, seed, coef, d_out);
         }
         if (st == FLTEE_GROUP_FALLBACK)  // one device (or a shape the group does not shard)
-            st = aggregate_records(c, aggregation_alg, n_agg, rpa, d, k_req, 0, d_out, seed, rec, packed,
+            st = aggregate_records(c, aggregation_alg, n_agg, rpa, d, k_req, 0, d_out, seed, rec, fmt,
                                    trim_count(n_agg, trim_pm));
     }
     if (!st && cfg.dp) {  // lib.rs:399-408 (a trimmed call: the n' - 2 t clients it averaged)
@@ -1290,6 +1311,15 @@ extern "C" void fltee_set_dense_trim(uint32_t per_mille) {
 
 extern "C" int fltee_upload_is_packed(int on, size_t d, size_t k_req, size_t ct_bytes) {
     return upload_is_packed(on != 0, d, k_req, ct_bytes) ? 1 : 0;
+}
+
+extern "C" void fltee_set_upload_bf16(int on) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    g_upload_bf16 = on != 0;
+}
+
+extern "C" int fltee_upload_is_bf16(int on, size_t d, size_t k_req, size_t ct_bytes) {
+    return upload_is_bf16(on != 0, d, k_req, ct_bytes) ? 1 : 0;
 }
 
 extern "C" void fltee_set_upload_aead_policy(int policy, size_t min_survivors) {

@@ -239,7 +239,9 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
     Plan p;
     // a packed upload (FLTEE_OPT_PACKED) is a dense one: n rows of values, k == d >= 2
     const bool packed = (o.flags & FLTEE_OPT_PACKED) != 0;
-    const bool dense = packed || (o.flags & FLTEE_OPT_DENSE) != 0;
+    // a bf16 upload (FLTEE_OPT_BF16) too: n rows of bf16 values, k == d >= 3, never with PACKED
+    const bool bf16 = (o.flags & FLTEE_OPT_BF16) != 0;
+    const bool dense = packed || bf16 || (o.flags & FLTEE_OPT_DENSE) != 0;
     const bool tree = alg == FLTEE_ALG_PATH_ORAM && (o.flags & FLTEE_OPT_ORAM_TREE);
     // the trimmed mean (FLTEE_OPT_TRIM, k_trim.hip): a dense or packed call on the flat algs
     // without the tree, 2 t < n, t <= FLTEE_TRIM_MAX; t = 0 is the untrimmed route itself
@@ -247,7 +249,8 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
     const size_t nrec = n * k, k_req = (o.flags & FLTEE_OPT_K_REQ) ? o.k_req : k;
     auto refuse_if = [&p](bool bad) { if (bad) p.status = FLTEE_ERROR_INVALID_PARAMETER; };
     // 32-bit positions; a dense upload has one record per parameter
-    refuse_if(n == 0 || nrec + d >= ((size_t)1 << 31) || (dense && k != d) || (packed && d < 2));
+    refuse_if(n == 0 || nrec + d >= ((size_t)1 << 31) || (dense && k != d) || (packed && d < 2) ||
+              (bf16 && (d < 3 || packed)));
     if (trim) {
         const bool flat = alg == FLTEE_ALG_BASELINE || alg == FLTEE_ALG_NON_OBLIVIOUS || alg == FLTEE_ALG_PATH_ORAM;
         refuse_if(!flat || !dense || (o.flags & (FLTEE_OPT_ORAM_TREE | FLTEE_OPT_ORAM_LAZY)) ||
@@ -271,7 +274,8 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
             // "client" of `slots` records: each index at most once, runs of <= 2 entries)
             if (lazy) plan_adv_bytes(p, p.adv = adv_shape(1, p.tree_slots, d, p.tree_slots, 1));
         } else if (dense) {
-            p.route = packed ? kRoutePacked : kRouteDense;
+            p.route = packed ? kRoutePacked : bf16 ? kRouteBf16 : kRouteDense;
+            // (a trimmed bf16 call: the records trim on the unpacked copy)
             if (trim && o.trim) p.route = packed ? kRouteTrimPacked : kRouteTrimDense;
         } else if (alg == FLTEE_ALG_NON_OBLIVIOUS && use_scatter_rows(n, k, d)) {
             p.route = kRouteScatterRows;
@@ -333,12 +337,13 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
         // FLTEE_OPT_DENSE on algs 1, 2, 6, 7 and on the tree only asserts k == d
         p.bytes[kWsCoef] = n * 4;
         p.clip_records = p.route != kRouteDense && p.route != kRoutePacked && p.route != kRouteTrimDense &&
-                         p.route != kRouteTrimPacked;
+                         p.route != kRouteTrimPacked && p.route != kRouteBf16;
         if (p.clip_records) p.bytes[kWsRec] = nrec * 8;
     }
-    // every route but the packed accumulate reads records: the plan (n, d, d) has, on the
+    // every route but the packed / bf16 accumulate reads records: the plan (n, d, d) has, on the
     // rows unpacked into the record scratch (where FLTEE_OPT_CLIP then clips them in place)
-    p.unpack = packed && p.route != kRoutePacked && p.route != kRouteTrimPacked;
+    p.unpack = (packed && p.route != kRoutePacked && p.route != kRouteTrimPacked) ||
+               (bf16 && p.route != kRouteBf16);
     if (p.unpack) p.bytes[kWsRec] = nrec * 8;
     return p;
 }
@@ -563,9 +568,10 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     const size_t n_avg = o.n_avg ? o.n_avg : (o.flags & FLTEE_OPT_TRIM) ? n - 2 * o.trim : n;
     const float coef = (o.flags & FLTEE_OPT_NO_AVERAGE) ? 1.0f : 1.0f / (float)n_avg;
 
-    // packed rows off the packed route: every alg below runs on the records (j, v[j])
+    // packed / bf16 rows off their own route: every alg below runs on the records (j, v[j])
     if (p.unpack) {
-        if (launch_unpack_dense(rec, n, d, (uint64_t *)c->ws_rec.ptr, s) != hipSuccess)
+        if (((o.flags & FLTEE_OPT_BF16) ? launch_unpack_bf16(rec, n, d, (uint64_t *)c->ws_rec.ptr, s)
+                                        : launch_unpack_dense(rec, n, d, (uint64_t *)c->ws_rec.ptr, s)) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
         rec = c->ws_rec.ptr;
     }
@@ -575,6 +581,7 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     if (o.flags & FLTEE_OPT_CLIP) {
         float *cf = (float *)c->ws_coef.ptr;
         if ((p.route == kRoutePacked || p.route == kRouteTrimPacked ? launch_packed_clip_coef(rec, n, d, o.clipping, cf, s)
+             : p.route == kRouteBf16                                ? launch_bf16_clip_coef(rec, n, d, o.clipping, cf, s)
                                      : launch_client_clip_coef(rec, n, k, o.clipping, cf, s)) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
         ccoef = cf;
@@ -609,6 +616,9 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
         break;
     case kRoutePacked:
         e = launch_dense_accumulate_packed(rec, n, d, coef, out, ccoef, acc, s);
+        break;
+    case kRouteBf16:
+        e = launch_dense_accumulate_bf16(rec, n, d, coef, out, ccoef, acc, s);
         break;
     case kRouteTrimDense:
     case kRouteTrimPacked:
@@ -754,6 +764,8 @@ extern "C" fltee_status_t fltee_aggregate_device(uint32_t alg, const void *d_rec
                                                  const fltee_device_opts *opts, void *stream) {
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
     const fltee_device_opts o = read_opts(opts);
+    // (bf16 rows are read as 2-byte halves: an odd base is refused by host arithmetic)
+    if ((o.flags & FLTEE_OPT_BF16) && ((uintptr_t)d_records & 1)) return FLTEE_ERROR_INVALID_PARAMETER;
     DeviceCtx *c = current_ctx();
     if (!c) return FLTEE_ERROR_UNEXPECTED;
     uint32_t *status = o.d_status ? o.d_status : c->status;
@@ -1206,6 +1218,27 @@ extern "C" fltee_status_t fltee_client_pack_dense_device(const float *d_values, 
     if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_values || !d_packed)
         return FLTEE_ERROR_INVALID_PARAMETER;
     return launch_pack_dense(d_values, n, d, d_packed, (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
+// ---- bf16 dense slices (k_bf16.hip) ---------------------------------------
+extern "C" size_t fltee_bf16_slice_bytes(size_t d) { return (d + 3) / 4 * 8; }
+
+extern "C" fltee_status_t fltee_unpack_bf16_device(const void *d_rows, size_t n, size_t d, void *d_records,
+                                                   void *stream) {
+    if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_rows || !d_records || ((uintptr_t)d_rows & 1))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    return launch_unpack_bf16(d_rows, n, d, (uint64_t *)d_records, (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_client_pack_bf16_device(const float *d_values, size_t n, size_t d,
+                                                        void *d_rows, void *stream) {
+    if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_values || !d_rows || ((uintptr_t)d_rows & 1))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    return launch_pack_bf16(d_values, n, d, d_rows, (hipStream_t)stream) == hipSuccess
                ? FLTEE_SUCCESS
                : FLTEE_ERROR_UNEXPECTED;
 }

@@ -50,6 +50,8 @@ OPT_PACKED = 0x100  # d_records: packed dense slices (value-only rows of 2 * cei
 OPT_TRIM = 0x200  # coordinate-wise trimmed mean of a dense call, DeviceOpts.trim clients a side
 TRIM_MAX = 64  # FLTEE_TRIM_MAX
 AAD_PACKED_BIT = 0x80000000  # FLTEE_AAD_PACKED_BIT: a packed call's last AAD word is alg | this
+OPT_BF16 = 0x400  # d_records: bf16 dense slices (value-only rows of 4 * ceil(d / 4) bf16)
+AAD_BF16_BIT = 0x40000000  # FLTEE_AAD_BF16_BIT: a bf16 call's last AAD word is alg | this
 
 
 class DeviceOpts(ctypes.Structure):
@@ -99,6 +101,11 @@ SIGNATURES = {
     "fltee_client_pack_dense_device": (_U32, [_P, _S, _S, _P, _P]),
     "fltee_trim_count": (_S, [_S, _U32]),
     "fltee_set_dense_trim": (None, [_U32]),
+    "fltee_bf16_slice_bytes": (_S, [_S]),
+    "fltee_upload_is_bf16": (ctypes.c_int, [ctypes.c_int, _S, _S, _S]),
+    "fltee_set_upload_bf16": (None, [ctypes.c_int]),
+    "fltee_unpack_bf16_device": (_U32, [_P, _S, _S, _P, _P]),
+    "fltee_client_pack_bf16_device": (_U32, [_P, _S, _S, _P, _P]),
     "fltee_set_upload_aead": (None, [ctypes.c_int]),
     "fltee_set_upload_aead_policy": (None, [ctypes.c_int, _S]),
     "fltee_auth_report": (_U32, [_U64, _U32, _P, _P, _S, _P]),

@@ -38,12 +38,12 @@ def unpack_records(rec):
 
 def opts(*, dense=False, dp=False, clip=False, accumulate=False, no_average=False, sigma=1.12,
          clipping=1.0, seed=0, k_req=None, batch=0, n_avg=0, fold_halo=0, status=None,
-         oram_tree=False, oram_lazy=False, packed=False, trim=None):
+         oram_tree=False, oram_lazy=False, packed=False, trim=None, bf16=False):
     o = L.DeviceOpts()
     o.flags = ((L.OPT_DENSE if dense else 0) | (L.OPT_DP if dp else 0) | (L.OPT_CLIP if clip else 0)
                | (L.OPT_ACCUMULATE if accumulate else 0) | (L.OPT_NO_AVERAGE if no_average else 0)
                | (L.OPT_ORAM_TREE if oram_tree else 0) | (L.OPT_ORAM_LAZY if oram_lazy else 0)
-               | (L.OPT_PACKED if packed else 0))
+               | (L.OPT_PACKED if packed else 0) | (L.OPT_BF16 if bf16 else 0))
     o.sigma, o.clipping, o.seed = sigma, clipping, seed
     if k_req is not None:
         o.flags |= L.OPT_K_REQ
@@ -64,8 +64,11 @@ def _check(st, what):
 def aggregate(alg, records, n, k, d, out=None, stream=None, **kw):
     """fltee_aggregate_device: aggregate n x k records (int64 cuda tensor) into out[d] (f32).
     packed=True: records is n packed slices instead (any cuda tensor of n * packed_row(d)
-    f32's worth of bytes: client c's d values, then one ignored f32 when d is odd; k == d)."""
-    if kw.get("packed"):
+    f32's worth of bytes: client c's d values, then one ignored f32 when d is odd; k == d).
+    bf16=True: n bf16 slices (n * bf16_row(d) halves' worth of bytes, 2-byte aligned)."""
+    if kw.get("bf16"):
+        assert records.is_cuda and records.numel() * records.element_size() >= n * bf16_row(d) * 2
+    elif kw.get("packed"):
         assert records.is_cuda and records.numel() * records.element_size() >= n * packed_row(d) * 4
     else:
         assert records.is_cuda and records.dtype == torch.int64 and records.numel() >= n * k
@@ -92,6 +95,23 @@ def unpack_dense(packed, n, d, records=None, stream=None):
         records = torch.empty(n * d, dtype=torch.int64, device=packed.device)
     _check(L.lib().fltee_unpack_dense_device(_ptr(packed), n, d, _ptr(records), _stream(stream)),
            "fltee_unpack_dense_device")
+    return records
+
+
+def bf16_row(d):
+    """bf16 slots of one bf16 slice of d parameters: 4 * ceil(d / 4)."""
+    return (d + 3) // 4 * 4
+
+
+def unpack_bf16(rows, n, d, records=None, stream=None):
+    """fltee_unpack_bf16_device: n bf16 slices ([n, bf16_row(d)] halves) -> int64 records
+    [n * d]: (j, widen(h[j])) per client."""
+    assert rows.is_cuda and rows.is_contiguous()
+    assert rows.numel() * rows.element_size() >= n * bf16_row(d) * 2
+    if records is None:
+        records = torch.empty(n * d, dtype=torch.int64, device=rows.device)
+    _check(L.lib().fltee_unpack_bf16_device(_ptr(rows), n, d, _ptr(records), _stream(stream)),
+           "fltee_unpack_bf16_device")
     return records
 
 

@@ -180,6 +180,22 @@ def upload_is_packed(on, d, k_req, ct_bytes):
     return bool(L.lib().fltee_upload_is_packed(1 if on else 0, d, k_req, ct_bytes))
 
 
+def set_upload_bf16(on):
+    """bf16 dense uploads (fltee_set_upload_bf16; off by default): while on, an
+    ecall_secure_aggregation call whose request declares a dense upload (num_of_sparse_parameters
+    0 or d, d >= 3) and whose clients each send exactly 8 * ceil(d / 4) ciphertext bytes (plus
+    the tag under AEAD) is read as bf16 slices (fltee.client.pack_dense_bf16 /
+    produce_payloads(bf16=True)): a quarter of the bytes, [out] the in-order f32 sum of the
+    widened values bit for bit.  Every other call is read as before; with set_upload_packed on
+    too, one server answers records, packed and bf16 uploads by their size."""
+    L.lib().fltee_set_upload_bf16(1 if on else 0)
+
+
+def upload_is_bf16(on, d, k_req, ct_bytes):
+    """fltee_upload_is_bf16: the bf16-call rule on one client's ciphertext bytes."""
+    return bool(L.lib().fltee_upload_is_bf16(1 if on else 0, d, k_req, ct_bytes))
+
+
 AEAD_POLICIES = {"abort": L.AEAD_ABORT, "report": L.AEAD_REPORT, "drop": L.AEAD_DROP}
 
 

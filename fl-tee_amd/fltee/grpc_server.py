@@ -9,7 +9,7 @@ code); the handlers are fltee.server.Aggregator, the server.rs logic over the C 
     python -m fltee.grpc_server [--address 0.0.0.0:50051] [--device 0] [--dp]
                                 [--strict-reference] [--quiet]
                                 [--aead [--aead-policy abort|report|drop]]
-                                [--packed-dense] [--trim-per-mille N]
+                                [--packed-dense] [--bf16-dense] [--trim-per-mille N]
 
 Like the reference: verbose on, dp off (server.rs:236-237; --dp turns DP on for
 the configs[3] runs), one enclave per process; calls are serialised by the
@@ -126,6 +126,9 @@ def main(argv=None):
     ap.add_argument("--packed-dense", action="store_true",
                     help="accept packed dense uploads: value-only slices of 8 * ceil(d / 2) bytes "
                          "per client (uploads of records are still answered as before)")
+    ap.add_argument("--bf16-dense", action="store_true",
+                    help="accept bf16 dense uploads: value-only slices of 8 * ceil(d / 4) bytes per "
+                         "client, widened exactly (other uploads are still answered as before)")
     ap.add_argument("--trim-per-mille", type=per_mille, default=0, metavar="N",
                     help="robust aggregation of dense uploads (algs 3, 4, 5): per coordinate the N "
                          "per mille smallest and largest client values are trimmed (0..500; 500: "
@@ -137,7 +140,8 @@ def main(argv=None):
     agg = Aggregator(device=args.device, verbose=not args.quiet, dp=args.dp,
                      strict_reference=args.strict_reference, aead=args.aead,
                      aead_policy=args.aead_policy or "abort", min_survivors=args.aead_min_survivors,
-                     packed=args.packed_dense, trim_per_mille=args.trim_per_mille)
+                     packed=args.packed_dense, trim_per_mille=args.trim_per_mille,
+                     bf16=args.bf16_dense)
     server, port = make_server(agg, args.address, verbose=not args.quiet)
     server.start()
     print(f"[Server] Now GRPC Server is binded on {args.address} (port {port})", flush=True)

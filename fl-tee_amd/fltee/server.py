@@ -23,6 +23,11 @@ request).  Documented deviations from the reference host:
     dense upload and carries 8 * ceil(d / 2) bytes per client (value-only slices,
     fltee.client.pack_dense) is aggregated from half the bytes, with the same reply; every
     other request, a dense 8 * d-byte one too, is answered as before.
+  * `bf16=True` (off by default) accepts bf16 dense uploads: a request that declares a dense
+    upload of d >= 3 parameters and carries 8 * ceil(d / 4) bytes per client (bf16 slices,
+    fltee.client.pack_dense_bf16) is aggregated from a quarter of the bytes — the in-order f32
+    sum of the values as sent; every other request is answered as before, and with `packed`
+    on too one server answers all three formats.
   * `trim_per_mille=N` (0, off, by default; 0..500) answers dense uploads to algs 3, 4, 5 with
     the coordinate-wise trimmed mean: per coordinate the N per mille smallest and largest
     client values are removed (500: the median), so a client sealing 1e30 or NaN no longer
@@ -34,7 +39,7 @@ import time
 
 from . import _lib as L
 from .ecalls import (AEAD_POLICIES, Enclave, set_dense_trim, set_upload_aead, set_upload_aead_policy,
-                     set_upload_packed)
+                     set_upload_bf16, set_upload_packed)
 
 
 class ServerPanic(RuntimeError):
@@ -54,7 +59,8 @@ def per_mille(text):
 
 class Aggregator:
     def __init__(self, device=0, verbose=False, dp=False, strict_reference=False, enclave=None,
-                 aead=False, aead_policy="abort", min_survivors=1, packed=False, trim_per_mille=0):
+                 aead=False, aead_policy="abort", min_survivors=1, packed=False, trim_per_mille=0,
+                 bf16=False):
         if aead_policy not in AEAD_POLICIES:
             raise ValueError(f"aead_policy must be one of {sorted(AEAD_POLICIES)}")
         if aead_policy != "abort" and not aead:
@@ -69,6 +75,9 @@ class Aggregator:
         self.packed = bool(packed)
         if self.packed:  # process-wide too
             set_upload_packed(True)
+        self.bf16 = bool(bf16)
+        if self.bf16:  # process-wide too
+            set_upload_bf16(True)
         self.trim_per_mille = int(trim_per_mille)
         if not 0 <= self.trim_per_mille <= 500:
             raise ValueError("trim_per_mille must be in 0..500")

@@ -241,6 +241,24 @@ fltee_status_t ecall_client_size_optimized_secure_aggregation(
                                       trim > FLTEE_TRIM_MAX, 2 * trim >= n, any other alg, a call
                                       that is not dense, FLTEE_OPT_ORAM_TREE / _LAZY */
 #define FLTEE_TRIM_MAX 64
+#define FLTEE_OPT_BF16 0x400u      /* d_records is the bf16 dense layout (below): n rows of
+                                      4 * ceil(d / 4) bf16, row c = client c's d values in position
+                                      order, then ignored padding; a value is widened exactly, f32
+                                      bits = (uint32)h << 16.  k must equal d and d >= 3, else
+                                      INVALID_PARAMETER; INVALID_PARAMETER also together with
+                                      FLTEE_OPT_PACKED and for a d_records that is not 2-byte
+                                      aligned.  Implies FLTEE_OPT_DENSE: algs 3, 4, 5 take the bf16
+                                      accumulate (no scratch; with FLTEE_OPT_CLIP the coefficients
+                                      only) and never set FLTEE_DEV_ERR_DENSE_ORDER.  Every other
+                                      alg, the tree (FLTEE_OPT_ORAM_TREE / _LAZY) and a call with
+                                      FLTEE_OPT_TRIM (t > 0) runs as it does for (n, d, d) on the
+                                      records (j, widen(h[j])) unpacked into the record scratch
+                                      (n * d * 8 bytes more of it; FLTEE_OPT_CLIP clips that copy in
+                                      place) — FLTEE_OPT_TRIM on algs 3, 4, 5 takes the records trim
+                                      there: a bf16 call is trimmed, never refused and never
+                                      silently untrimmed.  d_records is never written.  DP,
+                                      ACCUMULATE, NO_AVERAGE and n_avg mean what they mean on the
+                                      dense route */
 
 typedef struct fltee_device_opts {
     uint32_t flags;     /* FLTEE_OPT_* */
@@ -263,7 +281,8 @@ typedef struct fltee_device_opts {
 /* Aggregate n clients x k records (8 B each: u32 LE idx, f32 LE val),
  * client-major, into d_out[d] (overwritten, or accumulated with
  * FLTEE_OPT_ACCUMULATE).  With FLTEE_OPT_PACKED d_records is n packed slices
- * (value-only, 8 * ceil(d / 2) bytes each) instead.  Returns
+ * (value-only, 8 * ceil(d / 2) bytes each) instead, with FLTEE_OPT_BF16 n bf16
+ * slices (8 * ceil(d / 4) bytes each).  Returns
  * FLTEE_ERROR_INVALID_PARAMETER for host-detectable argument errors. */
 fltee_status_t fltee_aggregate_device(uint32_t alg, const void *d_records, size_t n, size_t k,
                                       size_t d, float *d_out, const fltee_device_opts *opts,
@@ -350,6 +369,55 @@ fltee_status_t fltee_unpack_dense_device(const void *d_packed, size_t n, size_t 
  * Sealing is fltee_encrypt_device / fltee_encrypt_auth_device with 8 U bytes per client. */
 fltee_status_t fltee_client_pack_dense_device(const float *d_values, size_t n, size_t d,
                                               void *d_packed, void *stream);
+
+/* ---- bf16 dense uploads: value-only slices at a quarter of the bytes ----------------------
+ * A client that quantises its update to bf16 sends the 16 bits it has.  With Q = ceil(d / 4), a
+ * BF16 slice is Q units of 8 bytes: the d little-endian bf16 values in position order, followed
+ * by 4 Q - d bf16 of padding (the client writes +0.0, the server ignores it).  A slice stays a
+ * whole number of 8-byte units, so the CTR / GCM kernels, the chunked load and the survivors
+ * gather work on "Q records per client" unchanged.
+ * Widening (server): f32 bits = (uint32)h << 16, exact for every bit pattern — NaN, +-inf and
+ * denormals included: [out] is the in-order f32 sum of the values the clients sent, bit for bit
+ * what the same values give as records.  Quantisation is the client's choice and the client's
+ * error; the server adds none.
+ * Narrowing (the producer below), with u = bits(x), in integer ops:
+ *     (u & 0x7FFFFFFF) > 0x7F800000 (NaN):  h = (u >> 16) | 0x0040   (the sign kept, quieted)
+ *     otherwise, round to nearest even:      h = (u + 0x7FFF + ((u >> 16) & 1)) >> 16
+ * (values just under FLT_MAX round to inf). */
+/* bytes of one bf16 slice of d parameters: 8 * ceil(d / 4) */
+size_t fltee_bf16_slice_bytes(size_t d);
+/* The bf16-call rule, the one place it is decided; the arguments are fltee_upload_is_packed's.
+ * Returns 1 when ecall_secure_aggregation reads the payload as bf16 slices:
+ *     on  &&  d >= 3  &&  k_req in {0, d} (the request declares a dense upload)
+ *         &&  ct_bytes == 8 * ceil(d / 4).
+ * For d >= 3 that size differs from a packed slice (8 * ceil(d / 2)) and from records (8 * d):
+ * both switches can be on and one server answers all three formats.  d < 3 is never bf16.  Host
+ * arithmetic. */
+int fltee_upload_is_bf16(int on, size_t d, size_t k_req, size_t ct_bytes);
+/* Process-wide, like fltee_set_upload_packed; off by default: every call is then launch for
+ * launch what it was.  On: an ecall_secure_aggregation call that the rule above accepts is
+ * loaded, decrypted, verified and (under FLTEE_AEAD_DROP) gathered as Q units per client, and
+ * aggregated with FLTEE_OPT_BF16 and k = d: algs 3, 4, 5 by the bf16 accumulate, algs 1, 2, 7
+ * and the tree on the unpacked records — [out] bit for bit what the widened values sent as
+ * (j, v[j]) records give.  The existing 0x2 refusals come first; advanced's "fold longer than
+ * the payload" refusal counts a slice as its d records.  fltee_set_dense_trim applies with n'
+ * and t as for a packed call (the trim runs on the unpacked records).  Under AEAD the last AAD
+ * word of a bf16 call is BE32(aggregation_alg | 0x40000000): a slice sealed for one of the three
+ * formats verifies under no other (0x3001).  On an eid over several GPUs the dense group path
+ * declines a bf16 call and the root runs it, every alg: the one-GPU bits.
+ * ecall_client_size_optimized_secure_aggregation (alg 6) ignores the switch. */
+void fltee_set_upload_bf16(int on);
+#define FLTEE_AAD_BF16_BIT 0x40000000u
+/* [n][4 Q] bf16 slices -> n * d records (j, widen(h[j])), client-major: what every route other
+ * than the bf16 accumulate runs on.  Asynchronous on `stream`.  d >= 1, d < 2^32; d_rows 2-byte
+ * aligned. */
+fltee_status_t fltee_unpack_bf16_device(const void *d_rows, size_t n, size_t d, void *d_records,
+                                        void *stream);
+/* The client producer: n clients' values [n][d] f32 -> [n][4 Q] bf16 slices, narrowed as above
+ * (padding +0.0).  Sealing is fltee_encrypt_device / fltee_encrypt_auth_device with 8 Q bytes
+ * per client. */
+fltee_status_t fltee_client_pack_bf16_device(const float *d_values, size_t n, size_t d, void *d_rows,
+                                             void *stream);
 
 /* ---- robust aggregation: the coordinate-wise trimmed mean / median behind the ECALL ----------
  * A client with a valid session key can seal an authentic slice of 1e30 or NaN; a plain mean
@@ -450,7 +518,8 @@ fltee_status_t fltee_debug_ghash_window_host(uint32_t client_id, const uint8_t *
  * ciphertext (B bytes) || tag (16 bytes) of the scheme above with
  *     IV  = BE32(fl_id) || BE32(round) || BE32(0)
  *     AAD = BE32(fl_id) || BE32(round) || BE32(client_id) || BE32(aggregation_alg)
- * (a packed call, fltee_set_upload_packed: BE32(aggregation_alg | 0x80000000)),
+ * (a packed call, fltee_set_upload_packed: BE32(aggregation_alg | 0x80000000); a bf16 call,
+ * fltee_set_upload_bf16: BE32(aggregation_alg | 0x40000000)),
  * so encrypted_parameters_size = n (B + 16) (alg 6 reads client_size (k 8 + 16) bytes) and
  * the records per client are floor(B / 8).  The existing refusals come first and stay 0x2;
  * a slice whose tag does not verify ends the call with *retval = FLTEE_ERROR_MAC_MISMATCH
