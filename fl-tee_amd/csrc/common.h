@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "fltee_agg.h"
+#include "rows.h"
 
 // One record of the wire / HBM layout: parameters.rs:3-10 Weight(u32 idx, f32 val),
 // little-endian, 8 bytes.  Kept as a u64 in registers: low word = idx, high = val bits.
@@ -156,31 +157,20 @@ hipError_t launch_scale(float *out, size_t d, float coef, hipStream_t s);
 hipError_t launch_check_range(const void *rec, size_t nrec, uint32_t limit, uint32_t *status,
                               hipStream_t s);
 
-// k_packed.hip: packed dense slices — n rows of 2 * ceil(d / 2) f32: a client's d values in
-// position order, then one ignored f32 when d is odd.  The packed accumulate has
-// launch_dense_accumulate's contract without the status word (there is no index to check);
-// clip_coef: launch_client_clip_coef's coefficients from a packed row; unpack: rows ->
-// n * d records (j, v[j]); pack: values [n][d] -> rows (padding +0.0).
-hipError_t launch_dense_accumulate_packed(const void *packed, size_t n, size_t d, float coef, float *out,
-                                          const float *client_coef, bool accumulate, hipStream_t s);
-hipError_t launch_packed_clip_coef(const void *packed, size_t n, size_t d, float clipping, float *coef,
-                                   hipStream_t s);
-hipError_t launch_unpack_dense(const void *packed, size_t n, size_t d, uint64_t *rec, hipStream_t s);
-hipError_t launch_pack_dense(const float *values, size_t n, size_t d, void *packed, hipStream_t s);
-void set_packed_variant(int v);
-
-// k_bf16.hip: bf16 dense slices — n rows of 4 * ceil(d / 4) bf16: a client's d values in
-// position order, then ignored padding; widened exactly (bits << 16).  The four launchers
-// are their packed siblings' contracts on these rows (pack narrows f32 to bf16, round to
-// nearest even in integer ops).
-hipError_t launch_dense_accumulate_bf16(const void *rows, size_t n, size_t d, float coef, float *out,
+// k_rows.hip: value-only dense slices (rows.h) — n rows of row_units(fmt, d) 8-byte units: a
+// client's d values in position order (kRowsF32: f32; kRowsBf16: bf16, widened exactly),
+// then ignored padding.  The accumulate has launch_dense_accumulate's contract without the
+// status word (there is no index to check); clip_coef: launch_client_clip_coef's
+// coefficients from a row; unpack: rows -> n * d records (j, v[j]); pack: f32 values [n][d]
+// -> rows (bf16: narrowed, round to nearest even in integer ops; padding +0.0).
+hipError_t launch_dense_accumulate_rows(RowFmt fmt, const void *rows, size_t n, size_t d, float coef, float *out,
                                         const float *client_coef, bool accumulate, hipStream_t s);
-hipError_t launch_bf16_clip_coef(const void *rows, size_t n, size_t d, float clipping, float *coef,
+hipError_t launch_rows_clip_coef(RowFmt fmt, const void *rows, size_t n, size_t d, float clipping, float *coef,
                                  hipStream_t s);
-hipError_t launch_unpack_bf16(const void *rows, size_t n, size_t d, uint64_t *rec, hipStream_t s);
-hipError_t launch_pack_bf16(const float *values, size_t n, size_t d, void *rows, hipStream_t s);
+hipError_t launch_unpack_rows(RowFmt fmt, const void *rows, size_t n, size_t d, uint64_t *rec, hipStream_t s);
+hipError_t launch_pack_rows(RowFmt fmt, const float *values, size_t n, size_t d, void *rows, hipStream_t s);
 
-// k_trim.hip: the coordinate-wise trimmed mean of n dense uploads (records, or packed rows),
+// k_trim.hip: the coordinate-wise trimmed mean of n dense uploads (records, or f32 rows),
 // t >= 1 clients removed on each side of every output; status: records only
 hipError_t launch_trimmed_mean(const void *in, bool packed, size_t n, size_t d, size_t t, float coef,
                                float *out, const float *client_coef, bool accumulate, uint32_t *status,

@@ -138,8 +138,8 @@ struct AuthReport {
 };
 static std::map<uint32_t, AuthReport> g_auth_reports;
 
-// ---- packed dense uploads (fltee_set_upload_packed; k_packed.hip) ---------------------
-static bool g_upload_packed = false;
+// ---- value-only dense uploads (fltee_set_upload_packed, fltee_set_upload_bf16; k_rows.hip) ----
+static bool g_upload_packed = false, g_upload_bf16 = false;
 // robust aggregation (fltee_set_dense_trim): the per-mille of clients trimmed on each side of
 // every coordinate of a dense call, 0 = off
 static uint32_t g_dense_trim = 0;
@@ -152,23 +152,26 @@ static size_t trim_count(size_t n, uint32_t per_mille) {
     return t < cap ? t : cap;
 }
 
-// The packed-call rule (include/fltee_agg.h fltee_upload_is_packed): the switch is on, the
-// request declares a dense upload of d >= 2 parameters, and every client's ciphertext is
-// exactly one packed slice (ct_bytes: 0 when the payload is not n equal slices).  d = 1 is
-// never packed: there a packed slice and a record are the same 8 bytes.
-static bool upload_is_packed(bool on, size_t d, size_t k_req, size_t ct_bytes) {
-    return on && d >= 2 && (k_req == 0 || k_req == d) && ct_bytes / 8 == (d + 1) / 2 && ct_bytes % 8 == 0;
+// The value-row rule (include/fltee_agg.h fltee_upload_is_packed, fltee_upload_is_bf16): the
+// format's switch is on, the request declares a dense upload of d >= rows_min_d parameters,
+// and every client's ciphertext is exactly one slice of the format (ct_bytes: 0 when the
+// payload is not n equal slices).  Below rows_min_d a slice has the size of a record (d = 1)
+// or, bf16 at d = 2, of an f32 slice; from there the three sizes differ, so one server
+// answers all three formats.
+static bool upload_is_rows(RowFmt f, bool on, size_t d, size_t k_req, size_t ct_bytes) {
+    return on && d >= rows_min_d(f) && (k_req == 0 || k_req == d) && ct_bytes / 8 == row_units(f, d) &&
+           ct_bytes % 8 == 0;
 }
 
-// ---- bf16 dense uploads (fltee_set_upload_bf16; k_bf16.hip) ---------------------------
-static bool g_upload_bf16 = false;
-
-// The bf16-call rule (include/fltee_agg.h fltee_upload_is_bf16): the packed rule on a slice of
-// 8 * ceil(d / 4) bytes.  d >= 3: below that a bf16 slice has the size of a packed slice
-// (d = 2) or of a record (d = 1); from there the three sizes differ, so one server answers
-// all three formats.
-static bool upload_is_bf16(bool on, size_t d, size_t k_req, size_t ct_bytes) {
-    return on && d >= 3 && (k_req == 0 || k_req == d) && ct_bytes / 8 == (d + 3) / 4 && ct_bytes % 8 == 0;
+// A call's upload format: the FLTEE_OPT_ flag its aggregate takes (0: records) and the bit its
+// AAD's alg word carries.  Packed is tried first.
+struct UploadFmt {
+    uint32_t opt, aad_bit;
+};
+static UploadFmt upload_format(bool packed_on, bool bf16_on, size_t d, size_t k_req, size_t ct_bytes) {
+    if (upload_is_rows(kRowsF32, packed_on, d, k_req, ct_bytes)) return {FLTEE_OPT_PACKED, FLTEE_AAD_PACKED_BIT};
+    if (upload_is_rows(kRowsBf16, bf16_on, d, k_req, ct_bytes)) return {FLTEE_OPT_BF16, FLTEE_AAD_BF16_BIT};
+    return {0u, 0u};
 }
 
 static bool keeps_verdict(bool aead) { return aead && g_aead_policy != FLTEE_AEAD_ABORT; }
@@ -755,21 +758,18 @@ extern "C" fltee_status_t ecall_secure_aggregation(
                  !gcm_sizes_ok(bpc - FLTEE_GCM_TAG_BYTES, 16)))
         return fail(FLTEE_ERROR_INVALID_PARAMETER);
     const size_t ctb = aead ? bpc - FLTEE_GCM_TAG_BYTES : bpc;
-    // packed dense slices (fltee_set_upload_packed): loaded, decrypted, verified and gathered
-    // as rpc = ceil(d / 2) 8-byte units per client, aggregated as rpa = d records
-    const bool packed = upload_is_packed(g_upload_packed, d, num_of_sparse_parameters,
-                                         encrypted_parameters_size % n ? 0 : ctb);
-    // bf16 dense slices (fltee_set_upload_bf16) likewise: rpc = ceil(d / 4) units per client
-    // (for d >= 3 no size is both a packed and a bf16 slice)
-    const bool bf16 = !packed && upload_is_bf16(g_upload_bf16, d, num_of_sparse_parameters,
-                                                encrypted_parameters_size % n ? 0 : ctb);
-    const uint32_t fmt = packed ? FLTEE_OPT_PACKED : bf16 ? FLTEE_OPT_BF16 : 0u;
+    // value-only slices (fltee_set_upload_packed, fltee_set_upload_bf16): loaded, decrypted,
+    // verified and gathered as rpc = row_units 8-byte units per client, aggregated as rpa = d
+    // records
+    const UploadFmt uf = upload_format(g_upload_packed, g_upload_bf16, d, num_of_sparse_parameters,
+                                       encrypted_parameters_size % n ? 0 : ctb);
+    const uint32_t fmt = uf.opt;
+    const bool packed = fmt == FLTEE_OPT_PACKED, bf16 = fmt == FLTEE_OPT_BF16;
     const size_t rpc = ctb / 8;
     const size_t rpa = fmt ? d : rpc;
     GcmArgs gcm;
     if (aead)
-        ecall_gcm_args(fl_id, round, client_ids, n,
-                       aggregation_alg | (packed ? FLTEE_AAD_PACKED_BIT : bf16 ? FLTEE_AAD_BF16_BIT : 0u), gcm);
+        ecall_gcm_args(fl_id, round, client_ids, n, aggregation_alg | uf.aad_bit, gcm);
     if ((aggregation_alg == FLTEE_ALG_ADVANCED || aggregation_alg == FLTEE_ALG_BUBBLE) &&
         n * num_of_sparse_parameters > n * rpa)
         return fail(FLTEE_ERROR_INVALID_PARAMETER);  // advanced.rs:72 out-of-bounds panic
@@ -911,7 +911,7 @@ extern "C" fltee_status_t ecall_secure_aggregation(
                 // engine's record scratch (no aggregate runs on the root before the ranks have
                 // taken their ranges) and the group proceeds as after any root load
                 if (!c->ws_rec.reserve(n * d * 8)) return fail(FLTEE_ERROR_OUT_OF_MEMORY);
-                if (launch_unpack_dense(c->records.ptr, n, d, (uint64_t *)c->ws_rec.ptr, c->stream) != hipSuccess ||
+                if (launch_unpack_rows(kRowsF32, c->records.ptr, n, d, (uint64_t *)c->ws_rec.ptr, c->stream) != hipSuccess ||
                     fl_stream_sync(c->stream) != hipSuccess)
                     return fail(FLTEE_ERROR_UNEXPECTED);
                 in.root_rec = (const uint64_t *)c->ws_rec.ptr;
@@ -1310,7 +1310,7 @@ extern "C" void fltee_set_dense_trim(uint32_t per_mille) {
 }
 
 extern "C" int fltee_upload_is_packed(int on, size_t d, size_t k_req, size_t ct_bytes) {
-    return upload_is_packed(on != 0, d, k_req, ct_bytes) ? 1 : 0;
+    return upload_is_rows(kRowsF32, on != 0, d, k_req, ct_bytes) ? 1 : 0;
 }
 
 extern "C" void fltee_set_upload_bf16(int on) {
@@ -1319,7 +1319,7 @@ extern "C" void fltee_set_upload_bf16(int on) {
 }
 
 extern "C" int fltee_upload_is_bf16(int on, size_t d, size_t k_req, size_t ct_bytes) {
-    return upload_is_bf16(on != 0, d, k_req, ct_bytes) ? 1 : 0;
+    return upload_is_rows(kRowsBf16, on != 0, d, k_req, ct_bytes) ? 1 : 0;
 }
 
 extern "C" void fltee_set_upload_aead_policy(int policy, size_t min_survivors) {

@@ -45,10 +45,10 @@ enum Route : uint32_t {
     kRouteBubble,        // alg 7: the stable network, then advanced's tail
     kRouteOptimized,     // alg 6: advanced per batch
     kRouteNips19,
-    kRoutePacked,        // flat algs, FLTEE_OPT_PACKED: the packed accumulate (k_packed.hip)
+    kRoutePacked,        // flat algs, FLTEE_OPT_PACKED: the packed accumulate (k_rows.hip)
     kRouteTrimDense,     // flat algs, FLTEE_OPT_TRIM with t > 0 on records: the trimmed mean (k_trim.hip)
     kRouteTrimPacked,    // ... on packed rows
-    kRouteBf16,          // flat algs, FLTEE_OPT_BF16: the bf16 accumulate (k_bf16.hip)
+    kRouteBf16,          // flat algs, FLTEE_OPT_BF16: the bf16 accumulate (k_rows.hip)
 };
 enum Tail : uint32_t {
     kTailNone,

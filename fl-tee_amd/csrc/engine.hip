@@ -235,13 +235,17 @@ static void plan_adv_bytes(Plan &p, const AdvShape &a) {
     if (a.stable) up(kWsS16, a.M * 16);
 }
 
+// the value-row format a call's flags name (rows.h); both flags together: the plan refuses
+static RowFmt row_format(uint32_t flags) {
+    return (flags & FLTEE_OPT_PACKED) ? kRowsF32 : (flags & FLTEE_OPT_BF16) ? kRowsBf16 : kRowsNone;
+}
+
 static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
     Plan p;
-    // a packed upload (FLTEE_OPT_PACKED) is a dense one: n rows of values, k == d >= 2
-    const bool packed = (o.flags & FLTEE_OPT_PACKED) != 0;
-    // a bf16 upload (FLTEE_OPT_BF16) too: n rows of bf16 values, k == d >= 3, never with PACKED
-    const bool bf16 = (o.flags & FLTEE_OPT_BF16) != 0;
-    const bool dense = packed || bf16 || (o.flags & FLTEE_OPT_DENSE) != 0;
+    // a value-row upload is a dense one: n rows of values, k == d >= rows_min_d (f32: 2, bf16: 3)
+    const RowFmt fmt = row_format(o.flags);
+    const bool packed = fmt == kRowsF32, bf16 = fmt == kRowsBf16;
+    const bool dense = fmt != kRowsNone || (o.flags & FLTEE_OPT_DENSE) != 0;
     const bool tree = alg == FLTEE_ALG_PATH_ORAM && (o.flags & FLTEE_OPT_ORAM_TREE);
     // the trimmed mean (FLTEE_OPT_TRIM, k_trim.hip): a dense or packed call on the flat algs
     // without the tree, 2 t < n, t <= FLTEE_TRIM_MAX; t = 0 is the untrimmed route itself
@@ -249,8 +253,9 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
     const size_t nrec = n * k, k_req = (o.flags & FLTEE_OPT_K_REQ) ? o.k_req : k;
     auto refuse_if = [&p](bool bad) { if (bad) p.status = FLTEE_ERROR_INVALID_PARAMETER; };
     // 32-bit positions; a dense upload has one record per parameter
-    refuse_if(n == 0 || nrec + d >= ((size_t)1 << 31) || (dense && k != d) || (packed && d < 2) ||
-              (bf16 && (d < 3 || packed)));
+    refuse_if(n == 0 || nrec + d >= ((size_t)1 << 31) || (dense && k != d) ||
+              (fmt != kRowsNone && d < rows_min_d(fmt)) ||
+              (o.flags & (FLTEE_OPT_PACKED | FLTEE_OPT_BF16)) == (FLTEE_OPT_PACKED | FLTEE_OPT_BF16));
     if (trim) {
         const bool flat = alg == FLTEE_ALG_BASELINE || alg == FLTEE_ALG_NON_OBLIVIOUS || alg == FLTEE_ALG_PATH_ORAM;
         refuse_if(!flat || !dense || (o.flags & (FLTEE_OPT_ORAM_TREE | FLTEE_OPT_ORAM_LAZY)) ||
@@ -342,8 +347,7 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
     }
     // every route but the packed / bf16 accumulate reads records: the plan (n, d, d) has, on the
     // rows unpacked into the record scratch (where FLTEE_OPT_CLIP then clips them in place)
-    p.unpack = (packed && p.route != kRoutePacked && p.route != kRouteTrimPacked) ||
-               (bf16 && p.route != kRouteBf16);
+    p.unpack = fmt != kRowsNone && p.route != kRoutePacked && p.route != kRouteTrimPacked && p.route != kRouteBf16;
     if (p.unpack) p.bytes[kWsRec] = nrec * 8;
     return p;
 }
@@ -569,9 +573,10 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     const float coef = (o.flags & FLTEE_OPT_NO_AVERAGE) ? 1.0f : 1.0f / (float)n_avg;
 
     // packed / bf16 rows off their own route: every alg below runs on the records (j, v[j])
+    // (fmt: what rec holds from here on)
+    const RowFmt sent = row_format(o.flags), fmt = p.unpack ? kRowsNone : sent;
     if (p.unpack) {
-        if (((o.flags & FLTEE_OPT_BF16) ? launch_unpack_bf16(rec, n, d, (uint64_t *)c->ws_rec.ptr, s)
-                                        : launch_unpack_dense(rec, n, d, (uint64_t *)c->ws_rec.ptr, s)) != hipSuccess)
+        if (launch_unpack_rows(sent, rec, n, d, (uint64_t *)c->ws_rec.ptr, s) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
         rec = c->ws_rec.ptr;
     }
@@ -580,9 +585,8 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     const float *ccoef = nullptr;
     if (o.flags & FLTEE_OPT_CLIP) {
         float *cf = (float *)c->ws_coef.ptr;
-        if ((p.route == kRoutePacked || p.route == kRouteTrimPacked ? launch_packed_clip_coef(rec, n, d, o.clipping, cf, s)
-             : p.route == kRouteBf16                                ? launch_bf16_clip_coef(rec, n, d, o.clipping, cf, s)
-                                     : launch_client_clip_coef(rec, n, k, o.clipping, cf, s)) != hipSuccess)
+        if ((fmt != kRowsNone ? launch_rows_clip_coef(fmt, rec, n, d, o.clipping, cf, s)
+                              : launch_client_clip_coef(rec, n, k, o.clipping, cf, s)) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
         ccoef = cf;
         if (p.clip_records) {
@@ -615,10 +619,8 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
         e = launch_dense_accumulate(rec, n, d, coef, out, ccoef, acc, status, s);
         break;
     case kRoutePacked:
-        e = launch_dense_accumulate_packed(rec, n, d, coef, out, ccoef, acc, s);
-        break;
     case kRouteBf16:
-        e = launch_dense_accumulate_bf16(rec, n, d, coef, out, ccoef, acc, s);
+        e = launch_dense_accumulate_rows(fmt, rec, n, d, coef, out, ccoef, acc, s);
         break;
     case kRouteTrimDense:
     case kRouteTrimPacked:
@@ -1201,14 +1203,14 @@ extern "C" size_t fltee_debug_net_log(size_t i, char *name, size_t name_cap, uin
     return nl;
 }
 
-// ---- packed dense slices (k_packed.hip) ----------------------------------
-extern "C" size_t fltee_packed_slice_bytes(size_t d) { return (d + 1) / 2 * 8; }
+// ---- value-only dense slices (k_rows.hip): f32 rows ... ------------------------
+extern "C" size_t fltee_packed_slice_bytes(size_t d) { return row_units(kRowsF32, d) * 8; }
 
 extern "C" fltee_status_t fltee_unpack_dense_device(const void *d_packed, size_t n, size_t d,
                                                     void *d_records, void *stream) {
     if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_packed || !d_records)
         return FLTEE_ERROR_INVALID_PARAMETER;
-    return launch_unpack_dense(d_packed, n, d, (uint64_t *)d_records, (hipStream_t)stream) == hipSuccess
+    return launch_unpack_rows(kRowsF32, d_packed, n, d, (uint64_t *)d_records, (hipStream_t)stream) == hipSuccess
                ? FLTEE_SUCCESS
                : FLTEE_ERROR_UNEXPECTED;
 }
@@ -1217,19 +1219,19 @@ extern "C" fltee_status_t fltee_client_pack_dense_device(const float *d_values, 
                                                          void *d_packed, void *stream) {
     if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_values || !d_packed)
         return FLTEE_ERROR_INVALID_PARAMETER;
-    return launch_pack_dense(d_values, n, d, d_packed, (hipStream_t)stream) == hipSuccess
+    return launch_pack_rows(kRowsF32, d_values, n, d, d_packed, (hipStream_t)stream) == hipSuccess
                ? FLTEE_SUCCESS
                : FLTEE_ERROR_UNEXPECTED;
 }
 
-// ---- bf16 dense slices (k_bf16.hip) ---------------------------------------
-extern "C" size_t fltee_bf16_slice_bytes(size_t d) { return (d + 3) / 4 * 8; }
+// ---- ... and bf16 rows ---------------------------------------------------------
+extern "C" size_t fltee_bf16_slice_bytes(size_t d) { return row_units(kRowsBf16, d) * 8; }
 
 extern "C" fltee_status_t fltee_unpack_bf16_device(const void *d_rows, size_t n, size_t d, void *d_records,
                                                    void *stream) {
     if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_rows || !d_records || ((uintptr_t)d_rows & 1))
         return FLTEE_ERROR_INVALID_PARAMETER;
-    return launch_unpack_bf16(d_rows, n, d, (uint64_t *)d_records, (hipStream_t)stream) == hipSuccess
+    return launch_unpack_rows(kRowsBf16, d_rows, n, d, (uint64_t *)d_records, (hipStream_t)stream) == hipSuccess
                ? FLTEE_SUCCESS
                : FLTEE_ERROR_UNEXPECTED;
 }
@@ -1238,7 +1240,7 @@ extern "C" fltee_status_t fltee_client_pack_bf16_device(const float *d_values, s
                                                         void *d_rows, void *stream) {
     if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_values || !d_rows || ((uintptr_t)d_rows & 1))
         return FLTEE_ERROR_INVALID_PARAMETER;
-    return launch_pack_bf16(d_values, n, d, d_rows, (hipStream_t)stream) == hipSuccess
+    return launch_pack_rows(kRowsBf16, d_values, n, d, d_rows, (hipStream_t)stream) == hipSuccess
                ? FLTEE_SUCCESS
                : FLTEE_ERROR_UNEXPECTED;
 }
@@ -1277,8 +1279,6 @@ extern "C" int fltee_debug_read_floor(const void *d_src, size_t bytes, void *d_s
 }
 // tuning hook (not part of the public header)
 extern "C" void fltee_debug_set_dense_variant(int v) { fltee::set_dense_variant(v); }
-// tuning hook: the packed accumulate's A/B launch shapes (k_packed.hip; 0 = shipped)
-extern "C" void fltee_debug_set_packed_variant(int v) { fltee::set_packed_variant(v); }
 // A/B hook: 0 runs advanced's second bitonic sort instead of the compaction network
 extern "C" void fltee_debug_set_advanced_compaction(int on) { fltee::g_advanced_compaction = on != 0; }
 extern "C" void fltee_debug_set_compact_variant(int v) { fltee::set_compact_variant(v); }

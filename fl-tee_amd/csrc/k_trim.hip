@@ -27,23 +27,16 @@
 // address or early exit.  The layouts:
 //   records : 8-byte (idx, val) loads, W = 1; idx != position raises
 //             FLTEE_DEV_ERR_DENSE_ORDER (reported, not followed), as dense_accumulate_v does.
-//   packed  : rows 2 ceil(d / 2) floats apart; W = 4 / 2 / 1 by dense_accumulate_p's
-//             alignment rules, capped by the lists' registers (T = 16: W <= 2; T = 64: W = 1,
-//             the lists alone are 128 registers an output).
+//   packed  : f32 rows (rows.h: the load, the stride, the store); W = 4 / 2 / 1 by rows_width,
+//             capped by the lists' registers (T = 16: W <= 2; T = 64: W = 1, the lists alone
+//             are 128 registers an output).
 //             The lanes of the last group past d never store: the padding float of an odd d
 //             reaches no output.
 #include "common.h"
 
 namespace fltee {
 
-typedef float tf32x4_t __attribute__((ext_vector_type(4)));
-typedef float tf32x2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t tu32x2_t __attribute__((ext_vector_type(2)));
-
-template <int W> struct TVec;
-template <> struct TVec<4> { typedef tf32x4_t type; };
-template <> struct TVec<2> { typedef tf32x2_t type; };
-template <> struct TVec<1> { typedef float type; };
 
 static __device__ __forceinline__ uint32_t trim_ord(float x) {
     const uint32_t b = __float_as_uint(x);
@@ -54,14 +47,10 @@ static __device__ __forceinline__ uint32_t trim_ord(float x) {
 template <bool PACKED, int W>
 static __device__ __forceinline__ void trim_load(const void *row, size_t j0, float (&x)[W], uint32_t &bad) {
     if constexpr (PACKED) {
-        typedef typename TVec<W>::type V;
-        const V v = __builtin_nontemporal_load(reinterpret_cast<const V *>((const float *)row + j0));
-        if constexpr (W == 1) {
-            x[0] = v;
-        } else {
+        uint32_t r[W];
+        RowF32::load<W>((const float *)row + j0, r);
 #pragma unroll
-            for (int w = 0; w < W; ++w) x[w] = v[w];
-        }
+        for (int w = 0; w < W; ++w) x[w] = RowF32::value<W>(r, w);
     } else {
         static_assert(PACKED || W == 1, "records: one 8-byte record a lane");
         const tu32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const tu32x2_t *>(row) + j0);
@@ -166,30 +155,11 @@ __global__ __launch_bounds__(256) void trimmed_mean_kernel(const uint8_t *__rest
         }
     }
 
-    float *o = out + j0;
-    if constexpr (W > 1) {
-        if (j0 + W <= d) {  // a whole group: one 4 W-byte store (out is 4 W-byte aligned)
-            typedef typename TVec<W>::type V;
-            V r;
-            if (acc_out) {
-                const V prev = *reinterpret_cast<const V *>(o);
-#pragma unroll
-                for (int w = 0; w < W; ++w) r[w] = __fadd_rn(prev[w], acc[w]);
-            } else {
-#pragma unroll
-                for (int w = 0; w < W; ++w) r[w] = __fmul_rn(acc[w], coef);
-            }
-            *reinterpret_cast<V *>(o) = r;
-            return;
-        }
-    }
-#pragma unroll
-    for (int w = 0; w < W; ++w)  // the d tail: the columns past d are dropped here
-        if (j0 + w < d) o[w] = acc_out ? __fadd_rn(o[w], acc[w]) : __fmul_rn(acc[w], coef);
+    rows_store<W>(out, j0, d, acc, coef, acc_out != 0);
     if (!PACKED && bad) atomicOr(status, FLTEE_DEV_ERR_DENSE_ORDER);
 }
 
-// Fewer outputs than this: too few waves to fill the SIMDs with 256-lane blocks (k_packed.hip's
+// Fewer outputs than this: too few waves to fill the SIMDs with 256-lane blocks (k_rows.hip's
 // small-d reasoning), so the lanes go out in 64-lane blocks — one wave a block, spread over
 // every CU.  The same work per lane: the same bits.
 constexpr size_t kTrimSmallD = (size_t)1 << 18;
@@ -224,11 +194,8 @@ hipError_t launch_trimmed_mean(const void *in, bool packed, size_t n, size_t d, 
         else launch_by_t<false, 1>(in, d * 8, n, d, t, coef, out, client_coef, accumulate, status, s);
         return hipGetLastError();
     }
-    const size_t stride = (d + 1) / 2 * 2;  // floats
-    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-    int W = 1;
-    if (a % 8 == 0 && b % 8 == 0) W = 2;  // (rows are always 8-byte multiples apart)
-    if (a % 16 == 0 && b % 16 == 0 && stride % 4 == 0) W = 4;
+    const size_t stride = RowF32::row_stride(d);  // floats
+    const int W = rows_width(kRowsF32, in, out, stride, d);
     if (t > 16) launch_t<true, 1, 64, 4>(in, stride * 4, n, d, t, coef, out, client_coef, accumulate, status, s);
     else if (W == 4) launch_by_t<true, 4>(in, stride * 4, n, d, t, coef, out, client_coef, accumulate, status, s);
     else if (W == 2) launch_by_t<true, 2>(in, stride * 4, n, d, t, coef, out, client_coef, accumulate, status, s);

@@ -157,7 +157,6 @@ EXTRA_SIGNATURES = {  # test hooks not in the public header
     "fltee_debug_gcm_subkeys": (ctypes.c_int, [_U32, _P, _P, ctypes.c_int]),
     "fltee_debug_gcm_segment_blocks": (_S, []),
     "fltee_debug_set_dense_variant": (None, [ctypes.c_int]),
-    "fltee_debug_set_packed_variant": (None, [ctypes.c_int]),
     "fltee_debug_set_oram_bucket": (None, [ctypes.c_int]),
     "fltee_debug_set_aes_variant": (None, [ctypes.c_int]),
     "fltee_debug_read_floor": (ctypes.c_int, [_P, _S, _P, ctypes.c_uint, _P]),

@@ -54,16 +54,19 @@ def serialize_dense(values, stream=None):
     return rec
 
 
+def _pack_rows(what, values, per_unit, dtype, stream):
+    v = _values(values)
+    n, d = v.shape
+    out = torch.empty((n, -(-d // per_unit) * per_unit), dtype=dtype, device=v.device)
+    _check(getattr(L.lib(), what)(_ptr(v), n, d, _ptr(out), _stream(stream)), what)
+    return out
+
+
 def pack_dense(values, stream=None):
     """[n, d] -> f32 [n, 2 * ceil(d / 2)]: the packed dense slices (fltee.ecalls.
     set_upload_packed) — each client's d values in position order, then one +0.0 when d is odd;
     half the bytes of serialize_dense."""
-    v = _values(values)
-    n, d = v.shape
-    out = torch.empty((n, (d + 1) // 2 * 2), dtype=torch.float32, device=v.device)
-    _check(L.lib().fltee_client_pack_dense_device(_ptr(v), n, d, _ptr(out), _stream(stream)),
-           "fltee_client_pack_dense_device")
-    return out
+    return _pack_rows("fltee_client_pack_dense_device", values, 2, torch.float32, stream)
 
 
 def pack_dense_bf16(values, stream=None):
@@ -72,12 +75,7 @@ def pack_dense_bf16(values, stream=None):
     keeps its sign and is quieted) in position order, then +0.0 up to a whole 8-byte unit; a
     quarter of the bytes of serialize_dense.  The server widens exactly: quantisation is the
     client's choice and the client's error."""
-    v = _values(values)
-    n, d = v.shape
-    out = torch.empty((n, (d + 3) // 4 * 4), dtype=torch.int16, device=v.device)
-    _check(L.lib().fltee_client_pack_bf16_device(_ptr(v), n, d, _ptr(out), _stream(stream)),
-           "fltee_client_pack_bf16_device")
-    return out
+    return _pack_rows("fltee_client_pack_bf16_device", values, 4, torch.int16, stream)
 
 
 def l2clipping(records, n, k, clipping, stream=None):

@@ -86,33 +86,30 @@ def packed_row(d):
     return (d + 1) // 2 * 2
 
 
-def unpack_dense(packed, n, d, records=None, stream=None):
-    """fltee_unpack_dense_device: n packed slices ([n, packed_row(d)] f32) -> int64 records
-    [n * d]: (j, v[j]) per client."""
-    assert packed.is_cuda and packed.is_contiguous()
-    assert packed.numel() * packed.element_size() >= n * packed_row(d) * 4
-    if records is None:
-        records = torch.empty(n * d, dtype=torch.int64, device=packed.device)
-    _check(L.lib().fltee_unpack_dense_device(_ptr(packed), n, d, _ptr(records), _stream(stream)),
-           "fltee_unpack_dense_device")
-    return records
-
-
 def bf16_row(d):
     """bf16 slots of one bf16 slice of d parameters: 4 * ceil(d / 4)."""
     return (d + 3) // 4 * 4
 
 
+def _unpack_rows(what, rows, row_bytes, n, d, records, stream):
+    assert rows.is_cuda and rows.is_contiguous()
+    assert rows.numel() * rows.element_size() >= n * row_bytes
+    if records is None:
+        records = torch.empty(n * d, dtype=torch.int64, device=rows.device)
+    _check(getattr(L.lib(), what)(_ptr(rows), n, d, _ptr(records), _stream(stream)), what)
+    return records
+
+
+def unpack_dense(packed, n, d, records=None, stream=None):
+    """fltee_unpack_dense_device: n packed slices ([n, packed_row(d)] f32) -> int64 records
+    [n * d]: (j, v[j]) per client."""
+    return _unpack_rows("fltee_unpack_dense_device", packed, packed_row(d) * 4, n, d, records, stream)
+
+
 def unpack_bf16(rows, n, d, records=None, stream=None):
     """fltee_unpack_bf16_device: n bf16 slices ([n, bf16_row(d)] halves) -> int64 records
     [n * d]: (j, widen(h[j])) per client."""
-    assert rows.is_cuda and rows.is_contiguous()
-    assert rows.numel() * rows.element_size() >= n * bf16_row(d) * 2
-    if records is None:
-        records = torch.empty(n * d, dtype=torch.int64, device=rows.device)
-    _check(L.lib().fltee_unpack_bf16_device(_ptr(rows), n, d, _ptr(records), _stream(stream)),
-           "fltee_unpack_bf16_device")
-    return records
+    return _unpack_rows("fltee_unpack_bf16_device", rows, bf16_row(d) * 2, n, d, records, stream)
 
 
 def reserve(alg, n, k, d, **kw):

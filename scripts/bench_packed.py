@@ -2,7 +2,7 @@
 values, in ONE process.
 
     python scripts/bench_packed.py [--shapes headline,c3] [--warmup 2] [--reps 5]
-                                   [--variants 0] [--eager] [--no-ecall] [--out FILE]
+                                   [--eager] [--no-ecall] [--out FILE]
 
 device  per shape (headline: 100 x 1M; c3 = configs[2] dense: 100 x 50,890): alg 3 on records
         (the dense accumulate) and on packed rows (the packed accumulate), and the streaming-
@@ -10,8 +10,7 @@ device  per shape (headline: 100 x 1M; c3 = configs[2] dense: 100 x 50,890): alg
         interleaved event-timed groups of `inner` calls of each (a group is captured once as a
         graph and replayed; --eager launches from the host); medians per call.  Every call
         reads a copy of its input that the calls before it have pushed out of the 256 MB
-        Infinity Cache (the copies rotate).  --variants: the packed accumulate's A/B launch
-        shapes (fltee_debug_set_packed_variant), each timed in the same interleaving.
+        Infinity Cache (the copies rotate).
 ecall   the host-inclusive alg-3 ECALL at 100 x 1M from pageable host memory, records against
         packed, CTR and AEAD: wall time and the call's three timers, medians of `reps`
         interleaved calls.
@@ -92,31 +91,22 @@ def device_rows(args, torch, np, L, C, D, name):
         assert lib.fltee_debug_read_floor(ctypes.c_void_p(b.data_ptr()), nbytes // 16 * 16,
                                           ctypes.c_void_p(sink.data_ptr()), 2048, stream) == 0
 
-    def packed_call(variant):
-        lib.fltee_debug_set_packed_variant(variant)
-        D.aggregate(3, nxt("pk", rows), n, d, d, out=out, packed=True)
-        lib.fltee_debug_set_packed_variant(0)
-
     calls = {"records": lambda: D.aggregate(3, nxt("rec", recs), n, d, d, out=out, dense=True),
              "records_floor": lambda: floor(recs, "rec", rec_bytes),
-             "packed_floor": lambda: floor(rows, "pk", pk_bytes)}
-    for v in args.variants:
-        calls["packed" if v == 0 else f"packed_v{v}"] = (lambda v=v: packed_call(v))
+             "packed_floor": lambda: floor(rows, "pk", pk_bytes),
+             "packed": lambda: D.aggregate(3, nxt("pk", rows), n, d, d, out=out, packed=True)}
     # the same bits first
     ref = D.aggregate(3, recs[0], n, d, d, dense=True)
-    for v in args.variants:
-        lib.fltee_debug_set_packed_variant(v)
-        got = D.aggregate(3, rows[0], n, d, d, packed=True)
-        lib.fltee_debug_set_packed_variant(0)
-        assert D.status() == 0 and torch.equal(got.view(torch.int32), ref.view(torch.int32)), v
+    got = D.aggregate(3, rows[0], n, d, d, packed=True)
+    assert D.status() == 0 and torch.equal(got.view(torch.int32), ref.view(torch.int32))
     med, mn = timed_groups(torch, np, calls, args.warmup, args.reps, args.inner, not args.eager)
     emit(args.out, dict(kind="device", shape=name, n=n, d=d, records_bytes=rec_bytes, packed_bytes=pk_bytes,
                         copies=dict(records=len(recs), packed=len(rows)), reps=args.reps, inner=args.inner,
                         timing="eager" if args.eager else "graph replay",
                         median_us=med, min_us=mn,
                         records_tb_per_s=rec_bytes / med["records"] / 1e6,
-                        packed_tb_per_s=pk_bytes / med["packed"] / 1e6 if "packed" in med else None,
-                        packed_over_records=med["packed"] / med["records"] if "packed" in med else None,
+                        packed_tb_per_s=pk_bytes / med["packed"] / 1e6,
+                        packed_over_records=med["packed"] / med["records"],
                         version=lib.fltee_version().decode()))
 
 
@@ -171,14 +161,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--inner", type=int, default=10, help="calls per event-timed group")
-    ap.add_argument("--variants", default="0", help="packed accumulate launch shapes to time (0 = shipped)")
     ap.add_argument("--eager", action="store_true",
                     help="launch every timed call from the host (default: each group captured once as a "
                          "graph and replayed, so a ~10 us call is not timed at the host's launch rate)")
     ap.add_argument("--no-ecall", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11", "packed.jsonl"))
     args = ap.parse_args()
-    args.variants = [int(v) for v in args.variants.split(",")]
     import numpy as np
     import torch
 

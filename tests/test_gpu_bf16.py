@@ -1,4 +1,4 @@
-"""FLTEE_OPT_BF16 on the device: the bf16 accumulate (k_bf16.hip) against the dense route on the
+"""FLTEE_OPT_BF16 on the device: the bf16 accumulate (k_rows.hip) against the dense route on the
 widened values serialized as records and against numpy's in-order f32 sum, bit for bit; every
 load width and the scalar path by the base's alignment; the options on the bf16 route against
 tests/options_model.py; every other alg, the tree and the trim on bf16 rows against the same call
@@ -30,7 +30,7 @@ pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
 
 SMALL_D = [3, 4, 5, 7, 8, 9, 15, 16, 17, 1023, 1025, 1028, 4097]
-T = 1 << 19  # k_bf16.hip kBf16SmallD
+T = 1 << 19  # rows.h kBf16SmallD
 LARGE_D = [50890, T - 8, T - 4, T, T + 4, T + 7]
 ALL_N = [1, 2, 15, 16, 17, 33, 65, 100]
 SEED = 0x5EED0001F00D

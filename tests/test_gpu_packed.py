@@ -1,4 +1,4 @@
-"""FLTEE_OPT_PACKED on the device: the packed accumulate (k_packed.hip) against the dense route
+"""FLTEE_OPT_PACKED on the device: the packed accumulate (k_rows.hip) against the dense route
 on the same values serialized as records and against numpy's in-order f32 sum, bit for bit;
 the options on the packed route against tests/options_model.py; every other alg on packed rows
 against the same call on the unpacked records; the producer round trip; and a reserved packed
