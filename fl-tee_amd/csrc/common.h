@@ -175,6 +175,12 @@ hipError_t launch_pack_rows(RowFmt fmt, const float *values, size_t n, size_t d,
 hipError_t launch_trimmed_mean(const void *in, bool packed, size_t n, size_t d, size_t t, float coef,
                                float *out, const float *client_coef, bool accumulate, uint32_t *status,
                                hipStream_t s);
+// k_trim_select.hip: the same contract at any t with 2 t < n, n <= FLTEE_TRIM_SELECT_MAX_N (the
+// thresholds by a bitwise descent over an LDS tile); columns: the tile's width for n, 0 past the cap
+hipError_t launch_trim_select(const void *in, bool packed, size_t n, size_t d, size_t t, float coef,
+                              float *out, const float *client_coef, bool accumulate, uint32_t *status,
+                              hipStream_t s);
+int trim_select_columns(size_t n);
 
 // k_bitonic.hip
 // valid: positions >= valid hold identical pad records (0: unknown); the stage blocks

@@ -143,6 +143,9 @@ static bool g_upload_packed = false, g_upload_bf16 = false;
 // robust aggregation (fltee_set_dense_trim): the per-mille of clients trimmed on each side of
 // every coordinate of a dense call, 0 = off
 static uint32_t g_dense_trim = 0;
+// fltee_set_dense_trim_select: a trimmed call with t > FLTEE_TRIM_MAX is answered by selection
+// (k_trim_select.hip) instead of refused; t <= FLTEE_TRIM_MAX stays on the list kernel
+static bool g_dense_trim_select = false;
 
 // The trim count (include/fltee_agg.h fltee_trim_count): the one place it is decided.
 static size_t trim_count(size_t n, uint32_t per_mille) {
@@ -386,6 +389,8 @@ static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d
     if (flat && rpc == d) o.flags |= FLTEE_OPT_DENSE;
     o.flags |= fmt;
     if (trim) o.flags |= FLTEE_OPT_TRIM, o.trim = trim;
+    // (t past the lists reaches here only under fltee_set_dense_trim_select: refused before otherwise)
+    if (trim > FLTEE_TRIM_MAX) o.flags |= FLTEE_OPT_TRIM_SELECT;
     if (ecall_takes_tree(alg, n, rpc, d)) o.flags |= FLTEE_OPT_ORAM_TREE;
     if (alg == FLTEE_ALG_NIPS19) o.seed = seed ? seed : next_seed();
     // advanced's fold (advanced.rs:66-101) runs once with halo = n: bit for bit for every
@@ -779,10 +784,12 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     // accumulate can be trimmed (a bf16 call: the records trim on its unpacked copy); a host
     // that switched trimming on never gets an untrimmed
     // mean back from any other — the sort-based algs, a sparse upload, the tree, a trim count
-    // past the kernel's lists (evaluated on the request as sent: n' <= n trims no more)
+    // past the kernel's lists (evaluated on the request as sent: n' <= n trims no more) unless
+    // fltee_set_dense_trim_select answers it by selection, n <= FLTEE_TRIM_SELECT_MAX_N
     const uint32_t trim_pm = g_dense_trim;
     if (trim_pm && (!flat || !(fmt || rpc == d) || (aggregation_alg == FLTEE_ALG_PATH_ORAM && oram_tree_default()) ||
-                    trim_count(n, trim_pm) > FLTEE_TRIM_MAX))
+                    (trim_count(n, trim_pm) > FLTEE_TRIM_MAX &&
+                     (!g_dense_trim_select || n > FLTEE_TRIM_SELECT_MAX_N))))
         return fail(FLTEE_ERROR_INVALID_PARAMETER);
 
     if (!c->outbuf.reserve(d * 4 + 16)) return fail(FLTEE_ERROR_OUT_OF_MEMORY);
@@ -1303,6 +1310,11 @@ extern "C" void fltee_set_upload_packed(int on) {
 }
 
 extern "C" size_t fltee_trim_count(size_t n, uint32_t per_mille) { return trim_count(n, per_mille); }
+
+extern "C" void fltee_set_dense_trim_select(int on) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    g_dense_trim_select = on != 0;
+}
 
 extern "C" void fltee_set_dense_trim(uint32_t per_mille) {
     std::lock_guard<std::recursive_mutex> lk(api_mutex());

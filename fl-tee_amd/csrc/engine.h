@@ -49,6 +49,8 @@ enum Route : uint32_t {
     kRouteTrimDense,     // flat algs, FLTEE_OPT_TRIM with t > 0 on records: the trimmed mean (k_trim.hip)
     kRouteTrimPacked,    // ... on packed rows
     kRouteBf16,          // flat algs, FLTEE_OPT_BF16: the bf16 accumulate (k_rows.hip)
+    kRouteTrimSelectDense,   // FLTEE_OPT_TRIM | _TRIM_SELECT with t > 0 on records: trim by selection (k_trim_select.hip)
+    kRouteTrimSelectPacked,  // ... on packed rows
 };
 enum Tail : uint32_t {
     kTailNone,

@@ -248,8 +248,10 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
     const bool dense = fmt != kRowsNone || (o.flags & FLTEE_OPT_DENSE) != 0;
     const bool tree = alg == FLTEE_ALG_PATH_ORAM && (o.flags & FLTEE_OPT_ORAM_TREE);
     // the trimmed mean (FLTEE_OPT_TRIM, k_trim.hip): a dense or packed call on the flat algs
-    // without the tree, 2 t < n, t <= FLTEE_TRIM_MAX; t = 0 is the untrimmed route itself
-    const bool trim = (o.flags & FLTEE_OPT_TRIM) != 0;
+    // without the tree, 2 t < n, t <= FLTEE_TRIM_MAX; t = 0 is the untrimmed route itself.
+    // With FLTEE_OPT_TRIM_SELECT (k_trim_select.hip) any t with 2 t < n, n <= FLTEE_TRIM_SELECT_MAX_N:
+    // the same refusals, the same scratch (none of its own)
+    const bool trim = (o.flags & FLTEE_OPT_TRIM) != 0, select = (o.flags & FLTEE_OPT_TRIM_SELECT) != 0;
     const size_t nrec = n * k, k_req = (o.flags & FLTEE_OPT_K_REQ) ? o.k_req : k;
     auto refuse_if = [&p](bool bad) { if (bad) p.status = FLTEE_ERROR_INVALID_PARAMETER; };
     // 32-bit positions; a dense upload has one record per parameter
@@ -259,8 +261,10 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
     if (trim) {
         const bool flat = alg == FLTEE_ALG_BASELINE || alg == FLTEE_ALG_NON_OBLIVIOUS || alg == FLTEE_ALG_PATH_ORAM;
         refuse_if(!flat || !dense || (o.flags & (FLTEE_OPT_ORAM_TREE | FLTEE_OPT_ORAM_LAZY)) ||
-                  o.trim > FLTEE_TRIM_MAX || 2 * o.trim >= n);
+                  (select ? n > FLTEE_TRIM_SELECT_MAX_N || o.trim >= n : o.trim > FLTEE_TRIM_MAX) ||
+                  2 * o.trim >= n);  // (o.trim >= n: 2 t may wrap)
     }
+    refuse_if(select && !trim);
     switch (alg) {
     case FLTEE_ALG_PATH_ORAM:
     case FLTEE_ALG_BASELINE:
@@ -281,7 +285,9 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
         } else if (dense) {
             p.route = packed ? kRoutePacked : bf16 ? kRouteBf16 : kRouteDense;
             // (a trimmed bf16 call: the records trim on the unpacked copy)
-            if (trim && o.trim) p.route = packed ? kRouteTrimPacked : kRouteTrimDense;
+            if (trim && o.trim)
+                p.route = select ? (packed ? kRouteTrimSelectPacked : kRouteTrimSelectDense)
+                                 : (packed ? kRouteTrimPacked : kRouteTrimDense);
         } else if (alg == FLTEE_ALG_NON_OBLIVIOUS && use_scatter_rows(n, k, d)) {
             p.route = kRouteScatterRows;
             p.bytes[kWsMat] = n * d * 4;
@@ -342,12 +348,14 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
         // FLTEE_OPT_DENSE on algs 1, 2, 6, 7 and on the tree only asserts k == d
         p.bytes[kWsCoef] = n * 4;
         p.clip_records = p.route != kRouteDense && p.route != kRoutePacked && p.route != kRouteTrimDense &&
-                         p.route != kRouteTrimPacked && p.route != kRouteBf16;
+                         p.route != kRouteTrimPacked && p.route != kRouteBf16 &&
+                         p.route != kRouteTrimSelectDense && p.route != kRouteTrimSelectPacked;
         if (p.clip_records) p.bytes[kWsRec] = nrec * 8;
     }
     // every route but the packed / bf16 accumulate reads records: the plan (n, d, d) has, on the
     // rows unpacked into the record scratch (where FLTEE_OPT_CLIP then clips them in place)
-    p.unpack = fmt != kRowsNone && p.route != kRoutePacked && p.route != kRouteTrimPacked && p.route != kRouteBf16;
+    p.unpack = fmt != kRowsNone && p.route != kRoutePacked && p.route != kRouteTrimPacked && p.route != kRouteBf16 &&
+               p.route != kRouteTrimSelectPacked;
     if (p.unpack) p.bytes[kWsRec] = nrec * 8;
     return p;
 }
@@ -626,6 +634,11 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     case kRouteTrimPacked:
         e = launch_trimmed_mean(rec, p.route == kRouteTrimPacked, n, d, o.trim, coef, out, ccoef, acc, status, s);
         break;
+    case kRouteTrimSelectDense:
+    case kRouteTrimSelectPacked:
+        e = launch_trim_select(rec, p.route == kRouteTrimSelectPacked, n, d, o.trim, coef, out, ccoef, acc, status,
+                               s);
+        break;
     case kRouteScatterRows:
         if (c->mat_clean_ptr != c->ws_mat.ptr || c->mat_clean_cap != c->ws_mat.cap) {
             c->mat_clean = 0;  // a new allocation: contents unknown
@@ -787,7 +800,7 @@ extern "C" fltee_status_t fltee_reserve(uint32_t alg, size_t n, size_t k, size_t
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
     const fltee_device_opts o = read_opts(opts);
     // a refused trimmed call is refused here too, by the plan, before anything is reserved
-    if ((o.flags & FLTEE_OPT_TRIM) && plan_status(alg, n, k, d, o) != FLTEE_SUCCESS)
+    if ((o.flags & (FLTEE_OPT_TRIM | FLTEE_OPT_TRIM_SELECT)) && plan_status(alg, n, k, d, o) != FLTEE_SUCCESS)
         return FLTEE_ERROR_INVALID_PARAMETER;
     return reserve(alg, n, k, d, o) ? FLTEE_SUCCESS : FLTEE_ERROR_OUT_OF_MEMORY;
 }

@@ -52,6 +52,8 @@ TRIM_MAX = 64  # FLTEE_TRIM_MAX
 AAD_PACKED_BIT = 0x80000000  # FLTEE_AAD_PACKED_BIT: a packed call's last AAD word is alg | this
 OPT_BF16 = 0x400  # d_records: bf16 dense slices (value-only rows of 4 * ceil(d / 4) bf16)
 AAD_BF16_BIT = 0x40000000  # FLTEE_AAD_BF16_BIT: a bf16 call's last AAD word is alg | this
+OPT_TRIM_SELECT = 0x800  # with OPT_TRIM: trim by selection (k_trim_select.hip), any trim with 2 * trim < n
+TRIM_SELECT_MAX_N = 4096  # FLTEE_TRIM_SELECT_MAX_N
 
 
 class DeviceOpts(ctypes.Structure):
@@ -101,6 +103,7 @@ SIGNATURES = {
     "fltee_client_pack_dense_device": (_U32, [_P, _S, _S, _P, _P]),
     "fltee_trim_count": (_S, [_S, _U32]),
     "fltee_set_dense_trim": (None, [_U32]),
+    "fltee_set_dense_trim_select": (None, [ctypes.c_int]),
     "fltee_bf16_slice_bytes": (_S, [_S]),
     "fltee_upload_is_bf16": (ctypes.c_int, [ctypes.c_int, _S, _S, _S]),
     "fltee_set_upload_bf16": (None, [ctypes.c_int]),

@@ -38,7 +38,7 @@ def unpack_records(rec):
 
 def opts(*, dense=False, dp=False, clip=False, accumulate=False, no_average=False, sigma=1.12,
          clipping=1.0, seed=0, k_req=None, batch=0, n_avg=0, fold_halo=0, status=None,
-         oram_tree=False, oram_lazy=False, packed=False, trim=None, bf16=False):
+         oram_tree=False, oram_lazy=False, packed=False, trim=None, bf16=False, trim_select=False):
     o = L.DeviceOpts()
     o.flags = ((L.OPT_DENSE if dense else 0) | (L.OPT_DP if dp else 0) | (L.OPT_CLIP if clip else 0)
                | (L.OPT_ACCUMULATE if accumulate else 0) | (L.OPT_NO_AVERAGE if no_average else 0)
@@ -52,6 +52,8 @@ def opts(*, dense=False, dp=False, clip=False, accumulate=False, no_average=Fals
     if trim is not None:  # the trimmed mean of a dense call: trim clients removed on each side
         o.flags |= L.OPT_TRIM
         o.trim = trim
+    if trim_select:  # ... by selection: any trim with 2 * trim < n, n <= TRIM_SELECT_MAX_N
+        o.flags |= L.OPT_TRIM_SELECT
     o.d_status = status.data_ptr() if status is not None else None
     return o
 

@@ -108,6 +108,10 @@ class Enclave:
         """fltee_set_dense_trim (process-wide; see the module function of the same name)."""
         set_dense_trim(per_mille)
 
+    def set_dense_trim_select(self, on):
+        """fltee_set_dense_trim_select (process-wide; see the module function of the same name)."""
+        set_dense_trim_select(on)
+
     def auth_report(self, fl_id):
         """fltee_auth_report: (round, [failed client ids in upload order]) of fl_id's last
         authenticated ECALL under the "report" / "drop" policies; an empty list after a clean
@@ -168,6 +172,14 @@ def set_dense_trim(per_mille):
     if not 0 <= int(per_mille) <= 500:
         raise ValueError(f"trim per mille {per_mille!r} is not in 0..500")
     L.lib().fltee_set_dense_trim(int(per_mille))
+
+
+def set_dense_trim_select(on):
+    """Trim by selection (fltee_set_dense_trim_select; off by default): while on, a call under
+    set_dense_trim whose trim count exceeds TRIM_MAX (the median from 131 clients on) is answered
+    by the selection kernel for up to TRIM_SELECT_MAX_N clients instead of ending with 0x2; a
+    call with a trim count up to TRIM_MAX runs as before."""
+    L.lib().fltee_set_dense_trim_select(1 if on else 0)
 
 
 def trim_count(n, per_mille):

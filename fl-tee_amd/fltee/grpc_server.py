@@ -9,7 +9,7 @@ code); the handlers are fltee.server.Aggregator, the server.rs logic over the C 
     python -m fltee.grpc_server [--address 0.0.0.0:50051] [--device 0] [--dp]
                                 [--strict-reference] [--quiet]
                                 [--aead [--aead-policy abort|report|drop]]
-                                [--packed-dense] [--bf16-dense] [--trim-per-mille N]
+                                [--packed-dense] [--bf16-dense] [--trim-per-mille N [--trim-select]]
 
 Like the reference: verbose on, dp off (server.rs:236-237; --dp turns DP on for
 the configs[3] runs), one enclave per process; calls are serialised by the
@@ -133,6 +133,9 @@ def main(argv=None):
                     help="robust aggregation of dense uploads (algs 3, 4, 5): per coordinate the N "
                          "per mille smallest and largest client values are trimmed (0..500; 500: "
                          "the median; 0: off); requests that cannot be trimmed are refused")
+    ap.add_argument("--trim-select", action="store_true",
+                    help="with --trim-per-mille: answer requests that trim more than 64 clients a "
+                         "side (up to 4096 clients) by the selection kernel instead of refusing them")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     if args.aead_policy is not None and not args.aead:
@@ -141,7 +144,7 @@ def main(argv=None):
                      strict_reference=args.strict_reference, aead=args.aead,
                      aead_policy=args.aead_policy or "abort", min_survivors=args.aead_min_survivors,
                      packed=args.packed_dense, trim_per_mille=args.trim_per_mille,
-                     bf16=args.bf16_dense)
+                     bf16=args.bf16_dense, trim_select=args.trim_select)
     server, port = make_server(agg, args.address, verbose=not args.quiet)
     server.start()
     print(f"[Server] Now GRPC Server is binded on {args.address} (port {port})", flush=True)

@@ -33,13 +33,16 @@ request).  Documented deviations from the reference host:
     client values are removed (500: the median), so a client sealing 1e30 or NaN no longer
     owns the round.  Every request that cannot be trimmed (another alg, a sparse upload) is a
     ServerPanic (retval 0x2), never an untrimmed mean.
+  * `trim_select=True` (off by default) lets `trim_per_mille` trim more than 64 clients a side
+    (the median from 131 clients on, up to 4096 clients): such a request is answered by the
+    selection kernel instead of refused; requests that trim up to 64 run as before.
 """
 import argparse
 import time
 
 from . import _lib as L
-from .ecalls import (AEAD_POLICIES, Enclave, set_dense_trim, set_upload_aead, set_upload_aead_policy,
-                     set_upload_bf16, set_upload_packed)
+from .ecalls import (AEAD_POLICIES, Enclave, set_dense_trim, set_dense_trim_select, set_upload_aead,
+                     set_upload_aead_policy, set_upload_bf16, set_upload_packed)
 
 
 class ServerPanic(RuntimeError):
@@ -60,7 +63,7 @@ def per_mille(text):
 class Aggregator:
     def __init__(self, device=0, verbose=False, dp=False, strict_reference=False, enclave=None,
                  aead=False, aead_policy="abort", min_survivors=1, packed=False, trim_per_mille=0,
-                 bf16=False):
+                 bf16=False, trim_select=False):
         if aead_policy not in AEAD_POLICIES:
             raise ValueError(f"aead_policy must be one of {sorted(AEAD_POLICIES)}")
         if aead_policy != "abort" and not aead:
@@ -83,6 +86,9 @@ class Aggregator:
             raise ValueError("trim_per_mille must be in 0..500")
         if self.trim_per_mille:  # process-wide too
             set_dense_trim(self.trim_per_mille)
+        self.trim_select = bool(trim_select)
+        if self.trim_select:  # process-wide too
+            set_dense_trim_select(True)
         self.verbose = verbose
         self.dp = dp
         self.strict_reference = strict_reference

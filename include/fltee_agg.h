@@ -241,6 +241,24 @@ fltee_status_t ecall_client_size_optimized_secure_aggregation(
                                       trim > FLTEE_TRIM_MAX, 2 * trim >= n, any other alg, a call
                                       that is not dense, FLTEE_OPT_ORAM_TREE / _LAZY */
 #define FLTEE_TRIM_MAX 64
+#define FLTEE_OPT_TRIM_SELECT 0x800u /* with FLTEE_OPT_TRIM and t > 0: trim by selection
+                                      (k_trim_select.hip) — the same definition, bit for bit, at any
+                                      t with 2 t < n; FLTEE_TRIM_MAX is the cap of the list kernel
+                                      above and does not apply.  The thresholds of an output (its
+                                      t-th smallest and t-th largest ord) come from a bitwise
+                                      descent on the 32-bit key, 32 rounds in which every value is
+                                      compared, over the call's n x C tile held in LDS: the input is
+                                      read once, at fixed addresses, and the launch shape depends on
+                                      (n, d) alone.  t <= FLTEE_TRIM_MAX is answered too (the same
+                                      bits as without the flag).  No scratch of its own: every
+                                      scratch size is that of the same call without the flag (a
+                                      FLTEE_OPT_BF16 call trims on its unpacked records, as there).
+                                      t = 0 is the untrimmed route.  Refused with INVALID_PARAMETER
+                                      by host arithmetic, before anything is reserved or launched:
+                                      n > FLTEE_TRIM_SELECT_MAX_N, the flag without FLTEE_OPT_TRIM,
+                                      and every refusal of FLTEE_OPT_TRIM other than
+                                      trim > FLTEE_TRIM_MAX */
+#define FLTEE_TRIM_SELECT_MAX_N 4096
 #define FLTEE_OPT_BF16 0x400u      /* d_records is the bf16 dense layout (below): n rows of
                                       4 * ceil(d / 4) bf16, row c = client c's d values in position
                                       order, then ignored padding; a value is widened exactly, f32
@@ -444,6 +462,15 @@ size_t fltee_trim_count(size_t n, uint32_t per_mille);
  * it: the one-GPU bits.  Nothing new is revealed: the launch shapes depend on (n', d, t) and
  * the buffers' alignment, all public. */
 void fltee_set_dense_trim(uint32_t per_mille);
+/* Process-wide; off by default: every call is then what it is above — t > FLTEE_TRIM_MAX (the
+ * median from 131 clients on) ends with 0x2.  On, under fltee_set_dense_trim: a call whose
+ * t = fltee_trim_count(n', per_mille) exceeds FLTEE_TRIM_MAX is aggregated with FLTEE_OPT_TRIM |
+ * FLTEE_OPT_TRIM_SELECT when the request's n <= FLTEE_TRIM_SELECT_MAX_N, and ends with 0x2 above
+ * it; a call with t <= FLTEE_TRIM_MAX stays on the list kernel, launch for launch.  Everything
+ * else about a trimmed call holds: n' under FLTEE_AEAD_DROP, the divisor n' - 2 t, the staged and
+ * the pipelined path, the refusals, the root running a multi-GPU eid's trimmed call.  Nothing
+ * new is revealed: the launch shapes depend on (n', d) and on whether t > FLTEE_TRIM_MAX. */
+void fltee_set_dense_trim_select(int on);
 
 /* ---- authenticated uploads: AES-128-GCM (NIST SP 800-38D), 96-bit IV, 128-bit tag ------
  * Per client: K = the session key, H = E_K(0^128), J0 = IV || 0x00000001, keystream block
