@@ -158,7 +158,8 @@ hipError_t launch_check_range(const void *rec, size_t nrec, uint32_t limit, uint
                               hipStream_t s);
 
 // k_rows.hip: value-only dense slices (rows.h) — n rows of row_units(fmt, d) 8-byte units: a
-// client's d values in position order (kRowsF32: f32; kRowsBf16: bf16, widened exactly),
+// client's d values in position order (kRowsF32: f32; kRowsBf16: bf16, widened exactly;
+// kRowsFp8: e4m3fn codes, widened exactly and multiplied by the f32 scale in the row's last unit),
 // then ignored padding.  The accumulate has launch_dense_accumulate's contract without the
 // status word (there is no index to check); clip_coef: launch_client_clip_coef's
 // coefficients from a row; unpack: rows -> n * d records (j, v[j]); pack: f32 values [n][d]
@@ -169,6 +170,9 @@ hipError_t launch_rows_clip_coef(RowFmt fmt, const void *rows, size_t n, size_t 
                                  hipStream_t s);
 hipError_t launch_unpack_rows(RowFmt fmt, const void *rows, size_t n, size_t d, uint64_t *rec, hipStream_t s);
 hipError_t launch_pack_rows(RowFmt fmt, const float *values, size_t n, size_t d, void *rows, hipStream_t s);
+// the fp8 producer (two launches: each client's scale into scale[n], then the quantise, which
+// writes the padding and the trailer too)
+hipError_t launch_pack_fp8(const float *values, size_t n, size_t d, float *scale, void *rows, hipStream_t s);
 
 // k_trim.hip: the coordinate-wise trimmed mean of n dense uploads (records, or f32 rows),
 // t >= 1 clients removed on each side of every output; status: records only

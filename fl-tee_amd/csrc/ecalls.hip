@@ -138,8 +138,8 @@ struct AuthReport {
 };
 static std::map<uint32_t, AuthReport> g_auth_reports;
 
-// ---- value-only dense uploads (fltee_set_upload_packed, fltee_set_upload_bf16; k_rows.hip) ----
-static bool g_upload_packed = false, g_upload_bf16 = false;
+// ---- value-only dense uploads (fltee_set_upload_packed, _bf16, _fp8; k_rows.hip) ----
+static bool g_upload_packed = false, g_upload_bf16 = false, g_upload_fp8 = false;
 // robust aggregation (fltee_set_dense_trim): the per-mille of clients trimmed on each side of
 // every coordinate of a dense call, 0 = off
 static uint32_t g_dense_trim = 0;
@@ -159,8 +159,8 @@ static size_t trim_count(size_t n, uint32_t per_mille) {
 // format's switch is on, the request declares a dense upload of d >= rows_min_d parameters,
 // and every client's ciphertext is exactly one slice of the format (ct_bytes: 0 when the
 // payload is not n equal slices).  Below rows_min_d a slice has the size of a record (d = 1)
-// or, bf16 at d = 2, of an f32 slice; from there the three sizes differ, so one server
-// answers all three formats.
+// or, bf16 at d = 2, of an f32 slice, or, fp8 at d <= 12, of a bf16 slice or more (rows.h
+// rows_min_d); from there the sizes differ, so one server answers all four formats.
 static bool upload_is_rows(RowFmt f, bool on, size_t d, size_t k_req, size_t ct_bytes) {
     return on && d >= rows_min_d(f) && (k_req == 0 || k_req == d) && ct_bytes / 8 == row_units(f, d) &&
            ct_bytes % 8 == 0;
@@ -171,9 +171,11 @@ static bool upload_is_rows(RowFmt f, bool on, size_t d, size_t k_req, size_t ct_
 struct UploadFmt {
     uint32_t opt, aad_bit;
 };
-static UploadFmt upload_format(bool packed_on, bool bf16_on, size_t d, size_t k_req, size_t ct_bytes) {
+static UploadFmt upload_format(bool packed_on, bool bf16_on, bool fp8_on, size_t d, size_t k_req,
+                               size_t ct_bytes) {
     if (upload_is_rows(kRowsF32, packed_on, d, k_req, ct_bytes)) return {FLTEE_OPT_PACKED, FLTEE_AAD_PACKED_BIT};
     if (upload_is_rows(kRowsBf16, bf16_on, d, k_req, ct_bytes)) return {FLTEE_OPT_BF16, FLTEE_AAD_BF16_BIT};
+    if (upload_is_rows(kRowsFp8, fp8_on, d, k_req, ct_bytes)) return {FLTEE_OPT_FP8, FLTEE_AAD_FP8_BIT};
     return {0u, 0u};
 }
 
@@ -205,8 +207,8 @@ static inline void put_be32(uint8_t *p, uint32_t v) {
 
 // What the ECALLs bind: IV = BE32(fl_id) || BE32(round) || BE32(0), AAD = BE32(fl_id) ||
 // BE32(round) || BE32(client_id) || BE32(aggregation_alg) — alg: a packed call passes
-// aggregation_alg | FLTEE_AAD_PACKED_BIT, a bf16 call aggregation_alg | FLTEE_AAD_BF16_BIT, so a
-// slice sealed for one format fails under the others
+// aggregation_alg | FLTEE_AAD_PACKED_BIT, a bf16 call aggregation_alg | FLTEE_AAD_BF16_BIT, an fp8
+// call aggregation_alg | FLTEE_AAD_FP8_BIT, so a slice sealed for one format fails under the others
 static void ecall_gcm_args(uint32_t fl_id, uint32_t round, const uint32_t *ids, size_t n,
                            uint32_t alg, GcmArgs &g) {
     put_be32(g.iv, fl_id);
@@ -374,8 +376,8 @@ static bool ecall_takes_tree(uint32_t alg, size_t n, size_t rpc, size_t d) {
 
 // The options aggregate_records gives aggregate() for an ECALL's alg (shared with the
 // staged path below).
-// rpc: the records per client the aggregate sees (a packed or bf16 call: d); fmt: c->records
-// holds value-only slices — FLTEE_OPT_PACKED or FLTEE_OPT_BF16, 0 for records
+// rpc: the records per client the aggregate sees (a packed, bf16 or fp8 call: d); fmt: c->records
+// holds value-only slices — FLTEE_OPT_PACKED, FLTEE_OPT_BF16 or FLTEE_OPT_FP8, 0 for records
 // trim: the call's trim count under fltee_set_dense_trim (0: an untrimmed call)
 static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d, size_t k_req,
                                     size_t batch, uint64_t seed, uint32_t fmt = 0, size_t trim = 0) {
@@ -763,13 +765,13 @@ extern "C" fltee_status_t ecall_secure_aggregation(
                  !gcm_sizes_ok(bpc - FLTEE_GCM_TAG_BYTES, 16)))
         return fail(FLTEE_ERROR_INVALID_PARAMETER);
     const size_t ctb = aead ? bpc - FLTEE_GCM_TAG_BYTES : bpc;
-    // value-only slices (fltee_set_upload_packed, fltee_set_upload_bf16): loaded, decrypted,
+    // value-only slices (fltee_set_upload_packed, _bf16, _fp8): loaded, decrypted,
     // verified and gathered as rpc = row_units 8-byte units per client, aggregated as rpa = d
     // records
-    const UploadFmt uf = upload_format(g_upload_packed, g_upload_bf16, d, num_of_sparse_parameters,
+    const UploadFmt uf = upload_format(g_upload_packed, g_upload_bf16, g_upload_fp8, d, num_of_sparse_parameters,
                                        encrypted_parameters_size % n ? 0 : ctb);
     const uint32_t fmt = uf.opt;
-    const bool packed = fmt == FLTEE_OPT_PACKED, bf16 = fmt == FLTEE_OPT_BF16;
+    const bool packed = fmt == FLTEE_OPT_PACKED, bf16 = fmt == FLTEE_OPT_BF16, fp8 = fmt == FLTEE_OPT_FP8;
     const size_t rpc = ctb / 8;
     const size_t rpa = fmt ? d : rpc;
     GcmArgs gcm;
@@ -781,7 +783,7 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     const bool flat = aggregation_alg == FLTEE_ALG_BASELINE || aggregation_alg == FLTEE_ALG_PATH_ORAM ||
                       aggregation_alg == FLTEE_ALG_NON_OBLIVIOUS;
     // robust aggregation (fltee_set_dense_trim): only a call that takes the dense or the packed
-    // accumulate can be trimmed (a bf16 call: the records trim on its unpacked copy); a host
+    // accumulate can be trimmed (a bf16 or fp8 call: the records trim on its unpacked copy); a host
     // that switched trimming on never gets an untrimmed
     // mean back from any other — the sort-based algs, a sparse upload, the tree, a trim count
     // past the kernel's lists (evaluated on the request as sent: n' <= n trims no more) unless
@@ -818,7 +820,7 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     bool verdict_stored = false;
     bool group_tried = false;  // a shape the group declined (or failed on) is not offered to it again
     const bool tree = ecall_takes_tree(aggregation_alg, n, rpa, d);
-    // (a packed or bf16 call is loaded on the root: the dense group path shards records by column;
+    // (a packed, bf16 or fp8 call is loaded on the root: the dense group path shards records by column;
     // a trimmed call too — it needs every client's value of a column in one place, which a
     // column shard has, but the group's per-rank sums are untrimmed: the root runs it)
     if (G && flat && !tree && !fmt && !trim_pm && rpc == d && bpc == d * 8 + tagb) {
@@ -842,8 +844,8 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     }
     // (the exact-runs policy folds on one GPU: one sequential walk of the sorted array)
     // (alg 7, once the host has opted in, shards like advanced: the same fold and tail)
-    // (a bf16 call is not sharded: the root runs it whole, the one-GPU bits)
-    const bool sharded = G && !bf16 &&
+    // (a bf16 or fp8 call is not sharded: the root runs it whole, the one-GPU bits)
+    const bool sharded = G && !bf16 && !fp8 &&
                          (((aggregation_alg == FLTEE_ALG_ADVANCED ||
                                  (aggregation_alg == FLTEE_ALG_BUBBLE && bubble_ecall_default())) &&
                            k_req == rpa && !exact_runs_default()) ||
@@ -1332,6 +1334,15 @@ extern "C" void fltee_set_upload_bf16(int on) {
 
 extern "C" int fltee_upload_is_bf16(int on, size_t d, size_t k_req, size_t ct_bytes) {
     return upload_is_rows(kRowsBf16, on != 0, d, k_req, ct_bytes) ? 1 : 0;
+}
+
+extern "C" void fltee_set_upload_fp8(int on) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    g_upload_fp8 = on != 0;
+}
+
+extern "C" int fltee_upload_is_fp8(int on, size_t d, size_t k_req, size_t ct_bytes) {
+    return upload_is_rows(kRowsFp8, on != 0, d, k_req, ct_bytes) ? 1 : 0;
 }
 
 extern "C" void fltee_set_upload_aead_policy(int policy, size_t min_survivors) {

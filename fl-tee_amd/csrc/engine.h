@@ -51,6 +51,7 @@ enum Route : uint32_t {
     kRouteBf16,          // flat algs, FLTEE_OPT_BF16: the bf16 accumulate (k_rows.hip)
     kRouteTrimSelectDense,   // FLTEE_OPT_TRIM | _TRIM_SELECT with t > 0 on records: trim by selection (k_trim_select.hip)
     kRouteTrimSelectPacked,  // ... on packed rows
+    kRouteFp8,           // flat algs, FLTEE_OPT_FP8: the fp8 accumulate (k_rows.hip)
 };
 enum Tail : uint32_t {
     kTailNone,
@@ -79,7 +80,7 @@ struct Plan {
     fltee_status_t status = FLTEE_SUCCESS;  // else the refusal; the sizes are still filled in
     Route route = kRouteNone;
     bool clip_records = false;  // FLTEE_OPT_CLIP works on a clipped copy of the records
-    bool unpack = false;        // FLTEE_OPT_PACKED / _BF16 off their own routes: the records are unpacked into ws_rec
+    bool unpack = false;        // FLTEE_OPT_PACKED / _BF16 / _FP8 off their own routes: the records are unpacked into ws_rec
     AdvShape adv;               // advanced, alg 7, an alg-6 batch, the lazy tree's readout (1 x slots)
     AdvShape adv_last;          // alg 6: the short last batch (when n % batch)
     size_t batch = 0;           // alg 6

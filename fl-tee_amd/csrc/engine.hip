@@ -235,16 +235,24 @@ static void plan_adv_bytes(Plan &p, const AdvShape &a) {
     if (a.stable) up(kWsS16, a.M * 16);
 }
 
-// the value-row format a call's flags name (rows.h); both flags together: the plan refuses
+// the value-row format a call's flags name (rows.h); two of the flags together: the plan refuses
 static RowFmt row_format(uint32_t flags) {
-    return (flags & FLTEE_OPT_PACKED) ? kRowsF32 : (flags & FLTEE_OPT_BF16) ? kRowsBf16 : kRowsNone;
+    return (flags & FLTEE_OPT_PACKED) ? kRowsF32
+           : (flags & FLTEE_OPT_BF16) ? kRowsBf16
+           : (flags & FLTEE_OPT_FP8)  ? kRowsFp8
+                                      : kRowsNone;
+}
+static bool one_row_flag(uint32_t flags) {
+    const uint32_t f = flags & (FLTEE_OPT_PACKED | FLTEE_OPT_BF16 | FLTEE_OPT_FP8);
+    return (f & (f - 1)) == 0;
 }
 
 static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
     Plan p;
-    // a value-row upload is a dense one: n rows of values, k == d >= rows_min_d (f32: 2, bf16: 3)
+    // a value-row upload is a dense one: n rows of values, k == d >= rows_min_d (f32: 2, bf16: 3,
+    // fp8: 13)
     const RowFmt fmt = row_format(o.flags);
-    const bool packed = fmt == kRowsF32, bf16 = fmt == kRowsBf16;
+    const bool packed = fmt == kRowsF32, bf16 = fmt == kRowsBf16, fp8 = fmt == kRowsFp8;
     const bool dense = fmt != kRowsNone || (o.flags & FLTEE_OPT_DENSE) != 0;
     const bool tree = alg == FLTEE_ALG_PATH_ORAM && (o.flags & FLTEE_OPT_ORAM_TREE);
     // the trimmed mean (FLTEE_OPT_TRIM, k_trim.hip): a dense or packed call on the flat algs
@@ -257,7 +265,7 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
     // 32-bit positions; a dense upload has one record per parameter
     refuse_if(n == 0 || nrec + d >= ((size_t)1 << 31) || (dense && k != d) ||
               (fmt != kRowsNone && d < rows_min_d(fmt)) ||
-              (o.flags & (FLTEE_OPT_PACKED | FLTEE_OPT_BF16)) == (FLTEE_OPT_PACKED | FLTEE_OPT_BF16));
+              !one_row_flag(o.flags));
     if (trim) {
         const bool flat = alg == FLTEE_ALG_BASELINE || alg == FLTEE_ALG_NON_OBLIVIOUS || alg == FLTEE_ALG_PATH_ORAM;
         refuse_if(!flat || !dense || (o.flags & (FLTEE_OPT_ORAM_TREE | FLTEE_OPT_ORAM_LAZY)) ||
@@ -283,8 +291,8 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
             // "client" of `slots` records: each index at most once, runs of <= 2 entries)
             if (lazy) plan_adv_bytes(p, p.adv = adv_shape(1, p.tree_slots, d, p.tree_slots, 1));
         } else if (dense) {
-            p.route = packed ? kRoutePacked : bf16 ? kRouteBf16 : kRouteDense;
-            // (a trimmed bf16 call: the records trim on the unpacked copy)
+            p.route = packed ? kRoutePacked : bf16 ? kRouteBf16 : fp8 ? kRouteFp8 : kRouteDense;
+            // (a trimmed bf16 or fp8 call: the records trim on the unpacked copy)
             if (trim && o.trim)
                 p.route = select ? (packed ? kRouteTrimSelectPacked : kRouteTrimSelectDense)
                                  : (packed ? kRouteTrimPacked : kRouteTrimDense);
@@ -348,14 +356,14 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
         // FLTEE_OPT_DENSE on algs 1, 2, 6, 7 and on the tree only asserts k == d
         p.bytes[kWsCoef] = n * 4;
         p.clip_records = p.route != kRouteDense && p.route != kRoutePacked && p.route != kRouteTrimDense &&
-                         p.route != kRouteTrimPacked && p.route != kRouteBf16 &&
+                         p.route != kRouteTrimPacked && p.route != kRouteBf16 && p.route != kRouteFp8 &&
                          p.route != kRouteTrimSelectDense && p.route != kRouteTrimSelectPacked;
         if (p.clip_records) p.bytes[kWsRec] = nrec * 8;
     }
-    // every route but the packed / bf16 accumulate reads records: the plan (n, d, d) has, on the
+    // every route but the packed / bf16 / fp8 accumulate reads records: the plan (n, d, d) has, on the
     // rows unpacked into the record scratch (where FLTEE_OPT_CLIP then clips them in place)
     p.unpack = fmt != kRowsNone && p.route != kRoutePacked && p.route != kRouteTrimPacked && p.route != kRouteBf16 &&
-               p.route != kRouteTrimSelectPacked;
+               p.route != kRouteTrimSelectPacked && p.route != kRouteFp8;
     if (p.unpack) p.bytes[kWsRec] = nrec * 8;
     return p;
 }
@@ -580,7 +588,7 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     const size_t n_avg = o.n_avg ? o.n_avg : (o.flags & FLTEE_OPT_TRIM) ? n - 2 * o.trim : n;
     const float coef = (o.flags & FLTEE_OPT_NO_AVERAGE) ? 1.0f : 1.0f / (float)n_avg;
 
-    // packed / bf16 rows off their own route: every alg below runs on the records (j, v[j])
+    // packed / bf16 / fp8 rows off their own route: every alg below runs on the records (j, v[j])
     // (fmt: what rec holds from here on)
     const RowFmt sent = row_format(o.flags), fmt = p.unpack ? kRowsNone : sent;
     if (p.unpack) {
@@ -628,6 +636,7 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
         break;
     case kRoutePacked:
     case kRouteBf16:
+    case kRouteFp8:
         e = launch_dense_accumulate_rows(fmt, rec, n, d, coef, out, ccoef, acc, s);
         break;
     case kRouteTrimDense:
@@ -781,6 +790,8 @@ extern "C" fltee_status_t fltee_aggregate_device(uint32_t alg, const void *d_rec
     const fltee_device_opts o = read_opts(opts);
     // (bf16 rows are read as 2-byte halves: an odd base is refused by host arithmetic)
     if ((o.flags & FLTEE_OPT_BF16) && ((uintptr_t)d_records & 1)) return FLTEE_ERROR_INVALID_PARAMETER;
+    // (fp8 rows carry an f32 scale, read as one: a base that is not 4-byte aligned likewise)
+    if ((o.flags & FLTEE_OPT_FP8) && ((uintptr_t)d_records & 3)) return FLTEE_ERROR_INVALID_PARAMETER;
     DeviceCtx *c = current_ctx();
     if (!c) return FLTEE_ERROR_UNEXPECTED;
     uint32_t *status = o.d_status ? o.d_status : c->status;
@@ -1254,6 +1265,32 @@ extern "C" fltee_status_t fltee_client_pack_bf16_device(const float *d_values, s
     if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_values || !d_rows || ((uintptr_t)d_rows & 1))
         return FLTEE_ERROR_INVALID_PARAMETER;
     return launch_pack_rows(kRowsBf16, d_values, n, d, d_rows, (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
+// ---- ... and fp8 rows (e4m3fn codes, a per-client f32 scale in the last unit) ------------
+extern "C" size_t fltee_fp8_slice_bytes(size_t d) { return row_units(kRowsFp8, d) * 8; }
+
+extern "C" fltee_status_t fltee_unpack_fp8_device(const void *d_rows, size_t n, size_t d, void *d_records,
+                                                  void *stream) {
+    if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_rows || !d_records || ((uintptr_t)d_rows & 3))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    return launch_unpack_rows(kRowsFp8, d_rows, n, d, (uint64_t *)d_records, (hipStream_t)stream) == hipSuccess
+               ? FLTEE_SUCCESS
+               : FLTEE_ERROR_UNEXPECTED;
+}
+
+extern "C" fltee_status_t fltee_client_pack_fp8_device(const float *d_values, size_t n, size_t d, void *d_rows,
+                                                       void *stream) {
+    if (n == 0 || d == 0 || d > 0xFFFFFFFFull || !d_values || !d_rows || ((uintptr_t)d_rows & 3))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    DeviceCtx *c = current_ctx();
+    if (!c) return FLTEE_ERROR_INVALID_PARAMETER;
+    // (the clients' scales between the two launches: the producers' coefficient scratch)
+    if (!c->ws_client_coef.reserve(n * 4)) return FLTEE_ERROR_OUT_OF_MEMORY;
+    return launch_pack_fp8(d_values, n, d, (float *)c->ws_client_coef.ptr, d_rows, (hipStream_t)stream) == hipSuccess
                ? FLTEE_SUCCESS
                : FLTEE_ERROR_UNEXPECTED;
 }

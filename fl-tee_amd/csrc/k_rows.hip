@@ -1,9 +1,10 @@
 // k_rows.hip — value-only dense uploads (gfx950): f32 rows at half the bytes of records
-// (FLTEE_OPT_PACKED), bf16 rows at a quarter (FLTEE_OPT_BF16).  rows.h describes the two
-// formats; every body here is written once over that description, and the __global__ entry
-// points below only name a format (their names are what the launch trace and a profiler show).
+// (FLTEE_OPT_PACKED), bf16 rows at a quarter (FLTEE_OPT_BF16), fp8 rows with a per-row f32 scale
+// at an eighth (FLTEE_OPT_FP8).  rows.h describes the three formats; every body here is written
+// once over that description, and the __global__ entry points below only name a format (their
+// names are what the launch trace and a profiler show).
 //
-// rows_accumulate (dense_accumulate_p / _h): k_accumulate.hip's dense_accumulate_v on value
+// rows_accumulate (dense_accumulate_p / _h / _q): k_accumulate.hip's dense_accumulate_v on value
 //   rows, under the same contract: out[j] = the in-order client sum ((+0.0 + v_0[j]) +
 //   v_1[j]) + ... with __fadd_rn over the (exactly widened) values, then * coef (or out +=
 //   with ACC; per-client clip coefficients with CLIP, v * cc rounded before the add as on the
@@ -16,8 +17,11 @@
 //   widest group the row base, the out base and the stride are aligned for — f32: 4 on 16
 //   bytes (U even), 2 on 8 (U odd — MLP-MNIST: d = 50,890, U = 25,445 — or a base at 8 mod
 //   16: the survivors buffer can land there), 1 below; bf16: 8 on 16 bytes and a large d, 4 on
-//   8, 2 on 4, 1 (a scalar 2-byte load) below.  The lanes of the last group past d never
-//   store: the padding reaches no output.
+//   8, 2 on 4, 1 (a scalar 2-byte load) below; fp8: 1 at a small d, else 4 on 4 bytes (out on 16),
+//   and 2 or 1 where the out base is off.  The lanes of the last group past d never
+//   store: the padding reaches no output.  A format with a per-row scale (fp8) reads it at the
+//   fixed element stride - 8 of the client's row — a wave-uniform load, once per client per lane
+//   group — and multiplies the widened value by it before the clip coefficient: two roundings.
 // rows_norm (packed_norm_kernel / bf16_norm_kernel): client_norm_kernel (k_dp.hip) on a value
 //   row: the same f64 sum of squares in the same lane order over the d widened values, so
 //   CLIP takes the same coefficients.
@@ -46,30 +50,43 @@ static __device__ __forceinline__ void rows_accumulate(size_t j0, const typename
     uint32_t c = 0;
     for (; c + UC <= n; c += UC) {
         uint32_t x[UC][R];
+        float sc[UC];
 #pragma unroll
         for (int u = 0; u < UC; ++u) F::template load<W>(p + (size_t)(c + u) * stride, x[u]);
+        if constexpr (F::kScaled) {
+#pragma unroll
+            for (int u = 0; u < UC; ++u) sc[u] = F::scale(rows + (size_t)(c + u) * stride, stride);
+        }
 #pragma unroll
         for (int u = 0; u < UC; ++u) {
             const float cc = CLIP ? ccoef[c + u] : 1.0f;
 #pragma unroll
             for (int w = 0; w < W; ++w) {
-                const float v = F::template value<W>(x[u], w);
+                const float q = F::template value<W>(x[u], w);
+                const float v = F::kScaled ? __fmul_rn(q, sc[u]) : q;  // (before the clip: two roundings)
                 acc[w] = __fadd_rn(acc[w], CLIP ? __fmul_rn(v, cc) : v);
             }
         }
     }
     if (c < n) {  // the n tail: one guarded batch (wave-uniform tests of the public n)
         uint32_t x[UC][R];
+        float sc[UC];
 #pragma unroll
         for (int u = 0; u < UC; ++u)
             if (c + u < n) F::template load<W>(p + (size_t)(c + u) * stride, x[u]);
+        if constexpr (F::kScaled) {
+#pragma unroll
+            for (int u = 0; u < UC; ++u)
+                if (c + u < n) sc[u] = F::scale(rows + (size_t)(c + u) * stride, stride);
+        }
 #pragma unroll
         for (int u = 0; u < UC; ++u) {
             if (c + u < n) {
                 const float cc = CLIP ? ccoef[c + u] : 1.0f;
 #pragma unroll
                 for (int w = 0; w < W; ++w) {
-                    const float v = F::template value<W>(x[u], w);
+                    const float q = F::template value<W>(x[u], w);
+                    const float v = F::kScaled ? __fmul_rn(q, sc[u]) : q;  // (before the clip: two roundings)
                     acc[w] = __fadd_rn(acc[w], CLIP ? __fmul_rn(v, cc) : v);
                 }
             }
@@ -84,9 +101,11 @@ static __device__ __forceinline__ void rows_norm(const typename F::elem *rows, s
                                                  size_t d, float clipping, float *coef) {
     __shared__ double part[4];
     const typename F::elem *src = rows + (size_t)blockIdx.x * stride;
+    float s = 1.0f;
+    if constexpr (F::kScaled) s = F::scale(src, stride);
     double ss = 0.0;
     for (size_t e = threadIdx.x; e < d; e += 256) {
-        const double v = (double)F::widen(src[e]);
+        const double v = (double)rows_scaled<F>(F::widen(src[e]), s);
         ss += v * v;
     }
     for (int o = 32; o > 0; o >>= 1) ss += __shfl_down(ss, o, 64);
@@ -107,7 +126,9 @@ static __device__ __forceinline__ void rows_unpack(const typename F::elem *rows,
     const size_t total = n * d;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         const size_t c = t / d, i = t - c * d;
-        rec[t] = make_rec((uint32_t)i, F::widen(rows[c * stride + i]));
+        float s = 1.0f;
+        if constexpr (F::kScaled) s = F::scale(rows + c * stride, stride);
+        rec[t] = make_rec((uint32_t)i, rows_scaled<F>(F::widen(rows[c * stride + i]), s));
     }
 }
 
@@ -118,6 +139,45 @@ static __device__ __forceinline__ void rows_pack(const float *values, size_t n, 
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         const size_t c = t / stride, i = t - c * stride;
         rows[t] = i < d ? F::narrow(values[c * d + i]) : (typename F::elem)0;
+    }
+}
+
+// The fp8 producer, two launches.  fp8_scale_kernel (a block a client): a = the largest finite
+// |v| of the row — a maximum over the bit patterns, so the order it is taken in changes nothing
+// — and s = a / 448 (f32, RN) where that is a normal, nonzero f32, else 1.  fp8_quantise_kernel:
+// a thread a byte of the row — the code of v / s (f32, RN), 0x00 padding up to 8 P, then the
+// trailer: s little-endian and 4 zero bytes.
+static __device__ __forceinline__ void fp8_row_scale(const float *values, size_t d, float *scale) {
+    __shared__ uint32_t part[4];
+    const float *src = values + (size_t)blockIdx.x * d;
+    uint32_t m = 0;
+    for (size_t e = threadIdx.x; e < d; e += 256) {
+        const uint32_t a = __float_as_uint(src[e]) & 0x7FFFFFFFu;
+        m = a < 0x7F800000u && a > m ? a : m;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_down((int)m, o, 64);
+        m = other > m ? other : m;
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) m = part[w] > m ? part[w] : m;
+        const float q = __fdiv_rn(__uint_as_float(m), 448.0f);
+        scale[blockIdx.x] = __float_as_uint(q) >= 0x00800000u ? q : 1.0f;  // (a is finite: so is q)
+    }
+}
+
+static __device__ __forceinline__ void fp8_row_quantise(const float *values, const float *scale, size_t n,
+                                                        size_t d, size_t stride, uint8_t *rows) {
+    const size_t total = n * stride;
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const size_t c = t / stride, i = t - c * stride;
+        const float s = scale[c];
+        uint8_t b = 0;
+        if (i < d) b = RowFp8::narrow(__fdiv_rn(values[c * d + i], s));
+        else if (i >= stride - 8 && i < stride - 4) b = (uint8_t)(__float_as_uint(s) >> (8 * (i - (stride - 8))));
+        rows[t] = b;
     }
 }
 
@@ -138,6 +198,14 @@ __global__ __launch_bounds__(NTH) void dense_accumulate_h(const uint16_t *__rest
     rows_accumulate<RowBf16, W, UC, CLIP, ACC>(((size_t)blockIdx.x * NTH + threadIdx.x) * W, rows, stride, d, n,
                                                coef, out, ccoef);
 }
+template <int W, int UC, bool CLIP, bool ACC, int NTH>
+__global__ __launch_bounds__(NTH) void dense_accumulate_q(const uint8_t *__restrict__ rows, size_t stride,
+                                                          size_t d, uint32_t n, float coef,
+                                                          float *__restrict__ out,
+                                                          const float *__restrict__ ccoef) {
+    rows_accumulate<RowFp8, W, UC, CLIP, ACC>(((size_t)blockIdx.x * NTH + threadIdx.x) * W, rows, stride, d, n,
+                                              coef, out, ccoef);
+}
 __global__ __launch_bounds__(256) void packed_norm_kernel(const float *__restrict__ pk, size_t stride,
                                                           size_t d, float clipping,
                                                           float *__restrict__ coef) {
@@ -148,6 +216,11 @@ __global__ __launch_bounds__(256) void bf16_norm_kernel(const uint16_t *__restri
                                                         float *__restrict__ coef) {
     rows_norm<RowBf16>(rows, stride, d, clipping, coef);
 }
+__global__ __launch_bounds__(256) void fp8_norm_kernel(const uint8_t *__restrict__ rows, size_t stride,
+                                                       size_t d, float clipping,
+                                                       float *__restrict__ coef) {
+    rows_norm<RowFp8>(rows, stride, d, clipping, coef);
+}
 __global__ void unpack_dense_kernel(const float *__restrict__ pk, size_t n, size_t d, size_t stride,
                                     uint64_t *__restrict__ rec) {
     rows_unpack<RowF32>(pk, n, d, stride, rec);
@@ -156,6 +229,10 @@ __global__ void unpack_bf16_kernel(const uint16_t *__restrict__ rows, size_t n, 
                                    uint64_t *__restrict__ rec) {
     rows_unpack<RowBf16>(rows, n, d, stride, rec);
 }
+__global__ void unpack_fp8_kernel(const uint8_t *__restrict__ rows, size_t n, size_t d, size_t stride,
+                                  uint64_t *__restrict__ rec) {
+    rows_unpack<RowFp8>(rows, n, d, stride, rec);
+}
 __global__ void pack_dense_kernel(const float *__restrict__ values, size_t n, size_t d, size_t stride,
                                   float *__restrict__ pk) {
     rows_pack<RowF32>(values, n, d, stride, pk);
@@ -163,6 +240,15 @@ __global__ void pack_dense_kernel(const float *__restrict__ values, size_t n, si
 __global__ void pack_bf16_kernel(const float *__restrict__ values, size_t n, size_t d, size_t stride,
                                  uint16_t *__restrict__ rows) {
     rows_pack<RowBf16>(values, n, d, stride, rows);
+}
+
+__global__ __launch_bounds__(256) void fp8_scale_kernel(const float *__restrict__ values, size_t d,
+                                                        float *__restrict__ scale) {
+    fp8_row_scale(values, d, scale);
+}
+__global__ void fp8_quantise_kernel(const float *__restrict__ values, const float *__restrict__ scale, size_t n,
+                                    size_t d, size_t stride, uint8_t *__restrict__ rows) {
+    fp8_row_quantise(values, scale, n, d, stride, rows);
 }
 
 // ---- the shipped launch shapes ---------------------------------------------------------
@@ -185,6 +271,11 @@ template <int W, int UC, bool CLIP, bool ACC, int NTH>
 static void launch_h(const AccArgs &a) {
     FLTEE_LAUNCH((dense_accumulate_h<W, UC, CLIP, ACC, NTH>), dim3(acc_blocks(a.d, W, NTH)), dim3(NTH), 0, a.s,
                  (const uint16_t *)a.rows, a.stride, a.d, (uint32_t)a.n, a.coef, a.out, a.ccoef);
+}
+template <int W, int UC, bool CLIP, bool ACC, int NTH>
+static void launch_q(const AccArgs &a) {
+    FLTEE_LAUNCH((dense_accumulate_q<W, UC, CLIP, ACC, NTH>), dim3(acc_blocks(a.d, W, NTH)), dim3(NTH), 0, a.s,
+                 (const uint8_t *)a.rows, a.stride, a.d, (uint32_t)a.n, a.coef, a.out, a.ccoef);
 }
 
 // Every shape computes the same adds in the same order: the same bits.  The A/B runs that
@@ -227,6 +318,25 @@ struct Bf16Shapes {
         else launch_h<1, 64, CLIP, ACC, 64>(a);
     }
 };
+// fp8 rows.  The decode is a dozen vector instructions a value, so the load-bound shapes of the
+// other formats are the wrong ones here (bf16's 64 in flight in 64-lane blocks: 60.4 us at
+// 100 x 1M and 40.6 us at 100 x 50,890 with 8 outputs a lane).  Measured over 14 to 18 shapes at
+// five sizes (profiles/r16/fp8.jsonl): 16 clients in flight win at every size; at
+// 100 x 1M 4 outputs a lane in 512-lane blocks take 44.5 us (8 outputs: 45.0 to 45.7; 16
+// outputs: 48.1 at best); at 100 x 50,890 one output a lane in 256-lane blocks takes 12.5 us
+// (2: 15.0; 4: 20.3 at best; 8: 27.6; 16: 46.2), at 100 x 262,152 22.3 us (4: 27.8).  So: one
+// output a lane below kFp8SmallD, up to 4 from there on where the alignment allows
+// (rows_width), 16 in flight throughout.  The scale of a client is one wave-uniform f32 load
+// beside its row's load.
+struct Fp8Shapes {
+    typedef RowFp8 F;
+    template <bool CLIP, bool ACC>
+    static void launch(int W, const AccArgs &a) {
+        if (W == 4) launch_q<4, 16, CLIP, ACC, 512>(a);
+        else if (W == 2) launch_q<2, 16, CLIP, ACC, 256>(a);
+        else launch_q<1, 16, CLIP, ACC, 256>(a);
+    }
+};
 
 template <class S>
 static hipError_t accumulate_rows(AccArgs a, bool accumulate) {
@@ -246,13 +356,18 @@ static hipError_t accumulate_rows(AccArgs a, bool accumulate) {
 hipError_t launch_dense_accumulate_rows(RowFmt fmt, const void *rows, size_t n, size_t d, float coef, float *out,
                                         const float *client_coef, bool accumulate, hipStream_t s) {
     const AccArgs a = {rows, 0, n, d, coef, out, client_coef, s};
-    return fmt == kRowsBf16 ? accumulate_rows<Bf16Shapes>(a, accumulate) : accumulate_rows<PackedShapes>(a, accumulate);
+    return fmt == kRowsFp8    ? accumulate_rows<Fp8Shapes>(a, accumulate)
+           : fmt == kRowsBf16 ? accumulate_rows<Bf16Shapes>(a, accumulate)
+                              : accumulate_rows<PackedShapes>(a, accumulate);
 }
 
 hipError_t launch_rows_clip_coef(RowFmt fmt, const void *rows, size_t n, size_t d, float clipping, float *coef,
                                  hipStream_t s) {
     if (n == 0) return hipSuccess;
-    if (fmt == kRowsBf16)
+    if (fmt == kRowsFp8)
+        FLTEE_LAUNCH(fp8_norm_kernel, dim3((unsigned)n), dim3(256), 0, s, (const uint8_t *)rows,
+                     RowFp8::row_stride(d), d, clipping, coef);
+    else if (fmt == kRowsBf16)
         FLTEE_LAUNCH(bf16_norm_kernel, dim3((unsigned)n), dim3(256), 0, s, (const uint16_t *)rows,
                      RowBf16::row_stride(d), d, clipping, coef);
     else
@@ -268,7 +383,10 @@ static unsigned rows_grid(size_t total) {
 
 hipError_t launch_unpack_rows(RowFmt fmt, const void *rows, size_t n, size_t d, uint64_t *rec, hipStream_t s) {
     if (n * d == 0) return hipSuccess;
-    if (fmt == kRowsBf16)
+    if (fmt == kRowsFp8)
+        FLTEE_LAUNCH(unpack_fp8_kernel, dim3(rows_grid(n * d)), dim3(256), 0, s, (const uint8_t *)rows, n, d,
+                     RowFp8::row_stride(d), rec);
+    else if (fmt == kRowsBf16)
         FLTEE_LAUNCH(unpack_bf16_kernel, dim3(rows_grid(n * d)), dim3(256), 0, s, (const uint16_t *)rows, n, d,
                      RowBf16::row_stride(d), rec);
     else
@@ -288,6 +406,16 @@ hipError_t launch_pack_rows(RowFmt fmt, const float *values, size_t n, size_t d,
         FLTEE_LAUNCH(pack_dense_kernel, dim3(rows_grid(n * stride)), dim3(256), 0, s, values, n, d, stride,
                      (float *)rows);
     }
+    return hipGetLastError();
+}
+
+// the fp8 producer: scale, n floats of scratch (launch 1 writes them, launch 2 reads them)
+hipError_t launch_pack_fp8(const float *values, size_t n, size_t d, float *scale, void *rows, hipStream_t s) {
+    if (n * d == 0) return hipSuccess;
+    const size_t stride = RowFp8::row_stride(d);
+    FLTEE_LAUNCH(fp8_scale_kernel, dim3((unsigned)n), dim3(256), 0, s, values, d, scale);
+    FLTEE_LAUNCH(fp8_quantise_kernel, dim3(rows_grid(n * stride)), dim3(256), 0, s, values, scale, n, d, stride,
+                 (uint8_t *)rows);
     return hipGetLastError();
 }
 

@@ -52,6 +52,8 @@ TRIM_MAX = 64  # FLTEE_TRIM_MAX
 AAD_PACKED_BIT = 0x80000000  # FLTEE_AAD_PACKED_BIT: a packed call's last AAD word is alg | this
 OPT_BF16 = 0x400  # d_records: bf16 dense slices (value-only rows of 4 * ceil(d / 4) bf16)
 AAD_BF16_BIT = 0x40000000  # FLTEE_AAD_BF16_BIT: a bf16 call's last AAD word is alg | this
+OPT_FP8 = 0x1000  # d_records: fp8 dense slices (8 * (ceil(d / 8) + 1) bytes: e4m3fn codes, then the f32 scale)
+AAD_FP8_BIT = 0x20000000  # FLTEE_AAD_FP8_BIT: an fp8 call's last AAD word is alg | this
 OPT_TRIM_SELECT = 0x800  # with OPT_TRIM: trim by selection (k_trim_select.hip), any trim with 2 * trim < n
 TRIM_SELECT_MAX_N = 4096  # FLTEE_TRIM_SELECT_MAX_N
 
@@ -109,6 +111,11 @@ SIGNATURES = {
     "fltee_set_upload_bf16": (None, [ctypes.c_int]),
     "fltee_unpack_bf16_device": (_U32, [_P, _S, _S, _P, _P]),
     "fltee_client_pack_bf16_device": (_U32, [_P, _S, _S, _P, _P]),
+    "fltee_fp8_slice_bytes": (_S, [_S]),
+    "fltee_upload_is_fp8": (ctypes.c_int, [ctypes.c_int, _S, _S, _S]),
+    "fltee_set_upload_fp8": (None, [ctypes.c_int]),
+    "fltee_unpack_fp8_device": (_U32, [_P, _S, _S, _P, _P]),
+    "fltee_client_pack_fp8_device": (_U32, [_P, _S, _S, _P, _P]),
     "fltee_set_upload_aead": (None, [ctypes.c_int]),
     "fltee_set_upload_aead_policy": (None, [ctypes.c_int, _S]),
     "fltee_auth_report": (_U32, [_U64, _U32, _P, _P, _S, _P]),

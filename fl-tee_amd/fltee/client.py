@@ -78,6 +78,22 @@ def pack_dense_bf16(values, stream=None):
     return _pack_rows("fltee_client_pack_bf16_device", values, 4, torch.int16, stream)
 
 
+def pack_dense_fp8(values, stream=None):
+    """[n, d] f32 -> uint8 [n, 8 * (ceil(d / 8) + 1)]: the fp8 dense slices (fltee.ecalls.
+    set_upload_fp8) — each client's d values as OCP e4m3fn codes of v / s (s = the row's largest
+    finite |v| / 448, or 1 where that is no normal f32; nearest code, ties to even, saturating at
+    448) in position order, 0x00 up to a whole 8-byte unit, then one unit more: s as a
+    little-endian f32 and 4 zero bytes.  An eighth of the bytes of serialize_dense, plus the
+    trailer.  The server widens exactly and multiplies by s once: quantisation is the client's
+    choice and the client's error."""
+    v = _values(values)
+    n, d = v.shape
+    out = torch.empty((n, 8 * (-(-d // 8) + 1)), dtype=torch.uint8, device=v.device)
+    _check(L.lib().fltee_client_pack_fp8_device(_ptr(v), n, d, _ptr(out), _stream(stream)),
+           "fltee_client_pack_fp8_device")
+    return out
+
+
 def l2clipping(records, n, k, clipping, stream=None):
     """In place on n clients x k records: val *= min(1, clipping / ||values||_2)."""
     assert records.is_cuda and records.dtype == torch.int64 and records.numel() >= n * k
@@ -105,15 +121,17 @@ def ecall_iv(fl_id, round_):
     return struct.pack(">III", fl_id, round_, 0)
 
 
-def ecall_aad(fl_id, round_, client_ids, aggregation_alg, packed=False, bf16=False):
+def ecall_aad(fl_id, round_, client_ids, aggregation_alg, packed=False, bf16=False, fp8=False):
     """The ECALLs' AAD, 16 bytes per client: BE32(fl_id) || BE32(round) || BE32(client_id) ||
     BE32(aggregation_alg) — a slice cannot be replayed in another round, moved to another
     client or submitted under another algorithm.  packed: the slices are packed dense values
     (pack_dense); the last word is BE32(aggregation_alg | 0x80000000), so a slice sealed as
     records never verifies as packed values, nor the other way round.  bf16: the slices are
-    bf16 values (pack_dense_bf16); the last word is BE32(aggregation_alg | 0x40000000)."""
-    assert not (packed and bf16)
-    word = aggregation_alg | (L.AAD_PACKED_BIT if packed else 0) | (L.AAD_BF16_BIT if bf16 else 0)
+    bf16 values (pack_dense_bf16); the last word is BE32(aggregation_alg | 0x40000000).  fp8: the
+    slices are fp8 codes with their scale (pack_dense_fp8); BE32(aggregation_alg | 0x20000000)."""
+    assert bool(packed) + bool(bf16) + bool(fp8) <= 1
+    word = (aggregation_alg | (L.AAD_PACKED_BIT if packed else 0) | (L.AAD_BF16_BIT if bf16 else 0)
+            | (L.AAD_FP8_BIT if fp8 else 0))
     return b"".join(struct.pack(">IIII", fl_id, round_, int(c), word) for c in client_ids)
 
 
@@ -135,31 +153,35 @@ def encrypt_parameters_gcm(records, client_ids, iv, aad=b"", stream=None):
 
 
 def encrypt_parameters_auth(records, client_ids, fl_id, round_, aggregation_alg, stream=None,
-                            packed=False, bf16=False):
+                            packed=False, bf16=False, fp8=False):
     """The authenticated upload of an ECALL (fltee.ecalls.set_upload_aead): the payload of
     ecall_secure_aggregation(fl_id, round_, client_ids, ..., aggregation_alg).  packed:
     `records` is pack_dense's tensor (any tensor is sealed by its bytes, n equal parts); bf16:
-    pack_dense_bf16's."""
+    pack_dense_bf16's; fp8: pack_dense_fp8's."""
     return encrypt_parameters_gcm(records, client_ids, ecall_iv(fl_id, round_),
-                                  ecall_aad(fl_id, round_, client_ids, aggregation_alg, packed, bf16),
+                                  ecall_aad(fl_id, round_, client_ids, aggregation_alg, packed, bf16, fp8),
                                   stream).reshape(-1)
 
 
-def produce_payloads(values, client_ids, k=None, clipping=None, stream=None, packed=False, bf16=False):
+def produce_payloads(values, client_ids, k=None, clipping=None, stream=None, packed=False, bf16=False,
+                     fp8=False):
     """fl_main.py:221-238 for every client at once: k=None -> dense uploads; packed (dense
     only): value-only slices of 8 * ceil(d / 2) bytes per client (pack_dense), for a server
     with fltee.ecalls.set_upload_packed(True); bf16 (dense only): bf16 slices of
     8 * ceil(d / 4) bytes per client (pack_dense_bf16), for a server with
-    fltee.ecalls.set_upload_bf16(True)."""
+    fltee.ecalls.set_upload_bf16(True); fp8 (dense only): fp8 slices of 8 * (ceil(d / 8) + 1)
+    bytes per client (pack_dense_fp8), for a server with fltee.ecalls.set_upload_fp8(True)."""
     v = _values(values)
     n, d = v.shape
     assert len(client_ids) == n
-    if packed or bf16:
-        assert not (packed and bf16) and (k is None or k == d), "packed and bf16 uploads are dense"
+    if packed or bf16 or fp8:
+        assert bool(packed) + bool(bf16) + bool(fp8) == 1 and (k is None or k == d), \
+            "packed, bf16 and fp8 uploads are dense"
         if clipping is not None:  # clipped as records (the reference's arithmetic), then packed
             rec = l2clipping(serialize_dense(v, stream), n, d, clipping, stream)
             v = rec.view(torch.float32).reshape(n, d, 2)[:, :, 1].contiguous()
-        return encrypt_parameters(pack_dense_bf16(v, stream) if bf16 else pack_dense(v, stream), client_ids, stream)
+        rows = pack_dense_fp8(v, stream) if fp8 else pack_dense_bf16(v, stream) if bf16 else pack_dense(v, stream)
+        return encrypt_parameters(rows, client_ids, stream)
     if k is None:
         rec, kk = serialize_dense(v, stream), d
     else:

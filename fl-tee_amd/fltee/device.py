@@ -38,12 +38,13 @@ def unpack_records(rec):
 
 def opts(*, dense=False, dp=False, clip=False, accumulate=False, no_average=False, sigma=1.12,
          clipping=1.0, seed=0, k_req=None, batch=0, n_avg=0, fold_halo=0, status=None,
-         oram_tree=False, oram_lazy=False, packed=False, trim=None, bf16=False, trim_select=False):
+         oram_tree=False, oram_lazy=False, packed=False, trim=None, bf16=False, trim_select=False,
+         fp8=False):
     o = L.DeviceOpts()
     o.flags = ((L.OPT_DENSE if dense else 0) | (L.OPT_DP if dp else 0) | (L.OPT_CLIP if clip else 0)
                | (L.OPT_ACCUMULATE if accumulate else 0) | (L.OPT_NO_AVERAGE if no_average else 0)
                | (L.OPT_ORAM_TREE if oram_tree else 0) | (L.OPT_ORAM_LAZY if oram_lazy else 0)
-               | (L.OPT_PACKED if packed else 0) | (L.OPT_BF16 if bf16 else 0))
+               | (L.OPT_PACKED if packed else 0) | (L.OPT_BF16 if bf16 else 0) | (L.OPT_FP8 if fp8 else 0))
     o.sigma, o.clipping, o.seed = sigma, clipping, seed
     if k_req is not None:
         o.flags |= L.OPT_K_REQ
@@ -67,8 +68,11 @@ def aggregate(alg, records, n, k, d, out=None, stream=None, **kw):
     """fltee_aggregate_device: aggregate n x k records (int64 cuda tensor) into out[d] (f32).
     packed=True: records is n packed slices instead (any cuda tensor of n * packed_row(d)
     f32's worth of bytes: client c's d values, then one ignored f32 when d is odd; k == d).
-    bf16=True: n bf16 slices (n * bf16_row(d) halves' worth of bytes, 2-byte aligned)."""
-    if kw.get("bf16"):
+    bf16=True: n bf16 slices (n * bf16_row(d) halves' worth of bytes, 2-byte aligned).
+    fp8=True: n fp8 slices (n * fp8_row(d) bytes, 4-byte aligned)."""
+    if kw.get("fp8"):
+        assert records.is_cuda and records.numel() * records.element_size() >= n * fp8_row(d)
+    elif kw.get("bf16"):
         assert records.is_cuda and records.numel() * records.element_size() >= n * bf16_row(d) * 2
     elif kw.get("packed"):
         assert records.is_cuda and records.numel() * records.element_size() >= n * packed_row(d) * 4
@@ -93,6 +97,12 @@ def bf16_row(d):
     return (d + 3) // 4 * 4
 
 
+def fp8_row(d):
+    """bytes of one fp8 slice of d parameters: 8 * (ceil(d / 8) + 1) — the codes, padding up
+    to the unit, then the unit that holds the f32 scale."""
+    return ((d + 7) // 8 + 1) * 8
+
+
 def _unpack_rows(what, rows, row_bytes, n, d, records, stream):
     assert rows.is_cuda and rows.is_contiguous()
     assert rows.numel() * rows.element_size() >= n * row_bytes
@@ -112,6 +122,12 @@ def unpack_bf16(rows, n, d, records=None, stream=None):
     """fltee_unpack_bf16_device: n bf16 slices ([n, bf16_row(d)] halves) -> int64 records
     [n * d]: (j, widen(h[j])) per client."""
     return _unpack_rows("fltee_unpack_bf16_device", rows, bf16_row(d) * 2, n, d, records, stream)
+
+
+def unpack_fp8(rows, n, d, records=None, stream=None):
+    """fltee_unpack_fp8_device: n fp8 slices ([n, fp8_row(d)] bytes) -> int64 records
+    [n * d]: (j, w(q[j]) * s) per client."""
+    return _unpack_rows("fltee_unpack_fp8_device", rows, fp8_row(d), n, d, records, stream)
 
 
 def reserve(alg, n, k, d, **kw):

@@ -208,6 +208,22 @@ def upload_is_bf16(on, d, k_req, ct_bytes):
     return bool(L.lib().fltee_upload_is_bf16(1 if on else 0, d, k_req, ct_bytes))
 
 
+def set_upload_fp8(on):
+    """fp8 dense uploads (fltee_set_upload_fp8; off by default): while on, an
+    ecall_secure_aggregation call that declares a dense upload of d >= 13 parameters and
+    carries 8 * (ceil(d / 8) + 1) bytes per client (plus the tag under AEAD) is read as fp8
+    slices (fltee.client.pack_dense_fp8 / produce_payloads(fp8=True)): e4m3fn codes and one f32
+    scale per client, [out] the in-order f32 sum of the values code * scale, bit for bit what
+    they give as records.  With set_upload_packed and set_upload_bf16 on too, one server answers
+    records, packed, bf16 and fp8 uploads by their size."""
+    L.lib().fltee_set_upload_fp8(1 if on else 0)
+
+
+def upload_is_fp8(on, d, k_req, ct_bytes):
+    """fltee_upload_is_fp8: the fp8-call rule on one client's ciphertext bytes."""
+    return bool(L.lib().fltee_upload_is_fp8(1 if on else 0, d, k_req, ct_bytes))
+
+
 AEAD_POLICIES = {"abort": L.AEAD_ABORT, "report": L.AEAD_REPORT, "drop": L.AEAD_DROP}
 
 

@@ -9,7 +9,7 @@ code); the handlers are fltee.server.Aggregator, the server.rs logic over the C 
     python -m fltee.grpc_server [--address 0.0.0.0:50051] [--device 0] [--dp]
                                 [--strict-reference] [--quiet]
                                 [--aead [--aead-policy abort|report|drop]]
-                                [--packed-dense] [--bf16-dense] [--trim-per-mille N [--trim-select]]
+                                [--packed-dense] [--bf16-dense] [--fp8-dense] [--trim-per-mille N [--trim-select]]
 
 Like the reference: verbose on, dp off (server.rs:236-237; --dp turns DP on for
 the configs[3] runs), one enclave per process; calls are serialised by the
@@ -129,6 +129,9 @@ def main(argv=None):
     ap.add_argument("--bf16-dense", action="store_true",
                     help="accept bf16 dense uploads: value-only slices of 8 * ceil(d / 4) bytes per "
                          "client, widened exactly (other uploads are still answered as before)")
+    ap.add_argument("--fp8-dense", action="store_true",
+                    help="accept fp8 dense uploads: e4m3fn codes and one f32 scale per client, "
+                         "8 * (ceil(d / 8) + 1) bytes (other uploads are still answered as before)")
     ap.add_argument("--trim-per-mille", type=per_mille, default=0, metavar="N",
                     help="robust aggregation of dense uploads (algs 3, 4, 5): per coordinate the N "
                          "per mille smallest and largest client values are trimmed (0..500; 500: "
@@ -144,7 +147,7 @@ def main(argv=None):
                      strict_reference=args.strict_reference, aead=args.aead,
                      aead_policy=args.aead_policy or "abort", min_survivors=args.aead_min_survivors,
                      packed=args.packed_dense, trim_per_mille=args.trim_per_mille,
-                     bf16=args.bf16_dense, trim_select=args.trim_select)
+                     bf16=args.bf16_dense, trim_select=args.trim_select, fp8=args.fp8_dense)
     server, port = make_server(agg, args.address, verbose=not args.quiet)
     server.start()
     print(f"[Server] Now GRPC Server is binded on {args.address} (port {port})", flush=True)

@@ -28,6 +28,11 @@ request).  Documented deviations from the reference host:
     fltee.client.pack_dense_bf16) is aggregated from a quarter of the bytes — the in-order f32
     sum of the values as sent; every other request is answered as before, and with `packed`
     on too one server answers all three formats.
+  * `fp8=True` (off by default) accepts fp8 dense uploads: a request that declares a dense
+    upload of d >= 13 parameters and carries 8 * (ceil(d / 8) + 1) bytes per client (e4m3fn
+    codes and one f32 scale, fltee.client.pack_dense_fp8) is aggregated from an eighth of the
+    bytes — the in-order f32 sum of the values code * scale; every other request is answered as
+    before, and with `packed` and `bf16` on too one server answers all four formats.
   * `trim_per_mille=N` (0, off, by default; 0..500) answers dense uploads to algs 3, 4, 5 with
     the coordinate-wise trimmed mean: per coordinate the N per mille smallest and largest
     client values are removed (500: the median), so a client sealing 1e30 or NaN no longer
@@ -42,7 +47,7 @@ import time
 
 from . import _lib as L
 from .ecalls import (AEAD_POLICIES, Enclave, set_dense_trim, set_dense_trim_select, set_upload_aead,
-                     set_upload_aead_policy, set_upload_bf16, set_upload_packed)
+                     set_upload_aead_policy, set_upload_bf16, set_upload_fp8, set_upload_packed)
 
 
 class ServerPanic(RuntimeError):
@@ -63,7 +68,7 @@ def per_mille(text):
 class Aggregator:
     def __init__(self, device=0, verbose=False, dp=False, strict_reference=False, enclave=None,
                  aead=False, aead_policy="abort", min_survivors=1, packed=False, trim_per_mille=0,
-                 bf16=False, trim_select=False):
+                 bf16=False, trim_select=False, fp8=False):
         if aead_policy not in AEAD_POLICIES:
             raise ValueError(f"aead_policy must be one of {sorted(AEAD_POLICIES)}")
         if aead_policy != "abort" and not aead:
@@ -81,6 +86,9 @@ class Aggregator:
         self.bf16 = bool(bf16)
         if self.bf16:  # process-wide too
             set_upload_bf16(True)
+        self.fp8 = bool(fp8)
+        if self.fp8:  # process-wide too
+            set_upload_fp8(True)
         self.trim_per_mille = int(trim_per_mille)
         if not 0 <= self.trim_per_mille <= 500:
             raise ValueError("trim_per_mille must be in 0..500")

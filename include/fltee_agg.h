@@ -277,6 +277,24 @@ fltee_status_t ecall_client_size_optimized_secure_aggregation(
                                       silently untrimmed.  d_records is never written.  DP,
                                       ACCUMULATE, NO_AVERAGE and n_avg mean what they mean on the
                                       dense route */
+#define FLTEE_OPT_FP8 0x1000u      /* d_records is the fp8 dense layout (below): n rows of
+                                      8 * (ceil(d / 8) + 1) bytes, row c = client c's d e4m3fn codes
+                                      in position order, ignored padding, then the client's f32
+                                      scale s and 4 ignored bytes; a value is x = w(q) * s, w exact,
+                                      the product rounded once (RN).  k must equal d and d >= 13,
+                                      else INVALID_PARAMETER; INVALID_PARAMETER also together with
+                                      FLTEE_OPT_PACKED or FLTEE_OPT_BF16 and for a d_records that is
+                                      not 4-byte aligned (the scale is read as an f32).  Implies
+                                      FLTEE_OPT_DENSE: algs 3, 4, 5 take the fp8 accumulate (no
+                                      scratch; with FLTEE_OPT_CLIP the coefficients only, taken
+                                      from the x values and applied to x: two roundings, scale
+                                      first) and never set FLTEE_DEV_ERR_DENSE_ORDER.  Every other
+                                      alg, the tree (FLTEE_OPT_ORAM_TREE / _LAZY) and a call with
+                                      FLTEE_OPT_TRIM (with or without _TRIM_SELECT, t > 0) runs as it
+                                      does for (n, d, d) on the records (j, x_j) unpacked into the
+                                      record scratch, exactly as a FLTEE_OPT_BF16 call does.
+                                      d_records is never written.  DP, ACCUMULATE, NO_AVERAGE and
+                                      n_avg mean what they mean on the dense route */
 
 typedef struct fltee_device_opts {
     uint32_t flags;     /* FLTEE_OPT_* */
@@ -300,7 +318,8 @@ typedef struct fltee_device_opts {
  * client-major, into d_out[d] (overwritten, or accumulated with
  * FLTEE_OPT_ACCUMULATE).  With FLTEE_OPT_PACKED d_records is n packed slices
  * (value-only, 8 * ceil(d / 2) bytes each) instead, with FLTEE_OPT_BF16 n bf16
- * slices (8 * ceil(d / 4) bytes each).  Returns
+ * slices (8 * ceil(d / 4) bytes each), with FLTEE_OPT_FP8 n fp8 slices
+ * (8 * (ceil(d / 8) + 1) bytes each).  Returns
  * FLTEE_ERROR_INVALID_PARAMETER for host-detectable argument errors. */
 fltee_status_t fltee_aggregate_device(uint32_t alg, const void *d_records, size_t n, size_t k,
                                       size_t d, float *d_out, const fltee_device_opts *opts,
@@ -437,6 +456,70 @@ fltee_status_t fltee_unpack_bf16_device(const void *d_rows, size_t n, size_t d, 
 fltee_status_t fltee_client_pack_bf16_device(const float *d_values, size_t n, size_t d, void *d_rows,
                                              void *stream);
 
+/* ---- fp8 dense uploads: value-only slices at an eighth of the bytes, with a client scale ------
+ * A client that compresses its update to 8 bits sends the codes and one scale.  With
+ * P = ceil(d / 8), an FP8 slice is P + 1 units of 8 bytes:
+ *   values   bytes [0, d): the d codes in position order; bytes [d, 8 P): padding (the client
+ *            writes 0x00, the server ignores it);
+ *   trailer  the last unit: the client's scale s as a little-endian f32, then 4 bytes the client
+ *            writes as zero and the server ignores.
+ * The trailer sits at the end so that the values start at the row base; a slice stays a whole
+ * number of 8-byte units, so the CTR / GCM kernels, the chunked load and the survivors gather
+ * work on "P + 1 records per client" unchanged.
+ * Code: OCP e4m3fn — 1 sign bit, 4 exponent bits (bias 7), 3 mantissa bits.  No infinities;
+ * S.1111.111 (0x7F, 0xFF) is NaN; the largest finite value is 448 (0x7E), the smallest
+ * subnormal 2^-9.
+ * Widening (server): w(q) is the exact f32 of the code; a NaN code widens to the bits
+ * sign << 31 | 0x7FC00000.  Then x = w(q) * s in f32, round to nearest even: the only rounding
+ * the server adds.  Everything else applies to x exactly as to a record's value: FLTEE_OPT_CLIP
+ * takes its f64 norm over the x values and rounds x * cc before the add; the sum is the in-order
+ * f32 sum.  [out] is bit for bit what the same x values give as records.
+ * The scale is taken as sent: NaN, +-inf, 0 and negative values are the client's own values, as a
+ * sealed 1e30 is; a trimmed call (fltee_set_dense_trim) deals with them.
+ * Narrowing (the producer below), per row: a = the largest finite |v_j|; s = a / 448 (f32, RN)
+ * when that quotient is a normal, nonzero f32, else s = 1; y = v_j / s (f32, RN); NaN ->
+ * sign | 0x7F; |y| > 448, +-inf included -> sign | 0x7E; otherwise the nearest representable
+ * e4m3 magnitude, ties to the even code; the sign is kept (-0.0 -> 0x80).  A maximum does not
+ * depend on the order it is taken in: the producer is deterministic. */
+/* bytes of one fp8 slice of d parameters: 8 * (ceil(d / 8) + 1) */
+size_t fltee_fp8_slice_bytes(size_t d);
+/* The fp8-call rule, the one place it is decided; the arguments are fltee_upload_is_packed's.
+ * Returns 1 when ecall_secure_aggregation reads the payload as fp8 slices:
+ *     on  &&  d >= 13  &&  k_req in {0, d} (the request declares a dense upload)
+ *         &&  ct_bytes == 8 * (ceil(d / 8) + 1).
+ * 13 is the smallest d from which that size differs from a bf16 slice at every d: for d = 9..12
+ * both are 24 bytes, and from 13 on ceil(d / 4) > ceil(d / 8) + 1; packed slices and records are
+ * larger at every d >= 13.  So with all three switches on one server answers four formats by
+ * their size.  Host arithmetic. */
+int fltee_upload_is_fp8(int on, size_t d, size_t k_req, size_t ct_bytes);
+/* Process-wide, like fltee_set_upload_bf16; off by default: every call is then launch for launch
+ * what it was.  On: an ecall_secure_aggregation call that the rule above accepts is loaded,
+ * decrypted, verified and (under FLTEE_AEAD_DROP) gathered as P + 1 units per client, and
+ * aggregated with FLTEE_OPT_FP8 and k = d: algs 3, 4, 5 by the fp8 accumulate, algs 1, 2, 7 and
+ * the tree on the unpacked records — [out] bit for bit what the x values sent as (j, x_j) records
+ * give.  The existing 0x2 refusals come first; advanced's "fold longer than the payload" refusal
+ * counts a slice as its d records.  fltee_set_dense_trim / _select apply as for a bf16 call (the
+ * trim runs on the unpacked records).  Under AEAD the last AAD word of an fp8 call is
+ * BE32(aggregation_alg | 0x20000000): a slice sealed for one of the four formats verifies under
+ * no other (0x3001).  On an eid over several GPUs the dense group path declines an fp8 call and
+ * the root runs it, every alg: the one-GPU bits.
+ * ecall_client_size_optimized_secure_aggregation (alg 6) ignores the switch. */
+void fltee_set_upload_fp8(int on);
+#define FLTEE_AAD_FP8_BIT 0x20000000u
+/* [n][8 (P + 1)] bytes of fp8 slices -> n * d records (j, w(q_j) * s), client-major: what every
+ * route other than the fp8 accumulate runs on.  Asynchronous on `stream`.  d >= 1, d < 2^32;
+ * d_rows 4-byte aligned. */
+fltee_status_t fltee_unpack_fp8_device(const void *d_rows, size_t n, size_t d, void *d_records,
+                                       void *stream);
+/* The client producer: n clients' values [n][d] f32 -> [n][8 (P + 1)] bytes of fp8 slices,
+ * narrowed as above, in two launches (each client's scale, then the quantise, which writes the
+ * padding and the trailer too).  Sealing is fltee_encrypt_device / fltee_encrypt_auth_device with
+ * 8 (P + 1) bytes per client.  d_rows 4-byte aligned.  The scales lie in the library's one
+ * producer scratch between the two launches (fltee_client_clip_device's coefficients use the same
+ * buffer): calls of the producers are serialised on one stream, not run concurrently on two. */
+fltee_status_t fltee_client_pack_fp8_device(const float *d_values, size_t n, size_t d, void *d_rows,
+                                            void *stream);
+
 /* ---- robust aggregation: the coordinate-wise trimmed mean / median behind the ECALL ----------
  * A client with a valid session key can seal an authentic slice of 1e30 or NaN; a plain mean
  * hands it the round, and the host cannot repair that afterwards (it never sees the updates).
@@ -546,7 +629,8 @@ fltee_status_t fltee_debug_ghash_window_host(uint32_t client_id, const uint8_t *
  *     IV  = BE32(fl_id) || BE32(round) || BE32(0)
  *     AAD = BE32(fl_id) || BE32(round) || BE32(client_id) || BE32(aggregation_alg)
  * (a packed call, fltee_set_upload_packed: BE32(aggregation_alg | 0x80000000); a bf16 call,
- * fltee_set_upload_bf16: BE32(aggregation_alg | 0x40000000)),
+ * fltee_set_upload_bf16: BE32(aggregation_alg | 0x40000000); an fp8 call,
+ * fltee_set_upload_fp8: BE32(aggregation_alg | 0x20000000)),
  * so encrypted_parameters_size = n (B + 16) (alg 6 reads client_size (k 8 + 16) bytes) and
  * the records per client are floor(B / 8).  The existing refusals come first and stay 0x2;
  * a slice whose tag does not verify ends the call with *retval = FLTEE_ERROR_MAC_MISMATCH
