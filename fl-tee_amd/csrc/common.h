@@ -186,6 +186,25 @@ hipError_t launch_trim_select(const void *in, bool packed, size_t n, size_t d, s
                               hipStream_t s);
 int trim_select_columns(size_t n);
 
+// k_krum.hip: Multi-Krum of n dense uploads (records, or f32 rows), n <= FLTEE_KRUM_MAX_N.
+// geometry: the padded rows (16 * tiles), the 128-row macro-tiles, and the Gram pass's column
+// chunks — functions of (n, d) alone; scratch_bytes: the chunks' partial matrices, G, the
+// scores and the keep words, in that order.  select: steps 1 - 4 (Gram, distances, scores,
+// ranking) into the scratch, where krum_scores / krum_keep find the n scores (f64) and keep
+// words (0 / ~0); status: records only.  accumulate: the dense accumulate's contract over the
+// clients whose keep word is set.
+struct KrumGeom {
+    size_t np, tiles, macros, chunk_cols, chunks;
+};
+KrumGeom krum_geometry(size_t n, size_t d);
+size_t krum_scratch_bytes(size_t n, size_t d);
+double *krum_scores(void *scratch, size_t n, size_t d);
+uint32_t *krum_keep(void *scratch, size_t n, size_t d);
+hipError_t launch_krum_select(const void *in, bool packed, size_t n, size_t d, size_t f, size_t m,
+                              const float *client_coef, void *scratch, uint32_t *status, hipStream_t s);
+hipError_t launch_krum_accumulate(const void *in, bool packed, size_t n, size_t d, const uint32_t *keep, float coef,
+                                  float *out, const float *client_coef, bool accumulate, hipStream_t s);
+
 // k_bitonic.hip
 // valid: positions >= valid hold identical pad records (0: unknown); the stage blocks
 // made of pads alone are skipped (exact, data-independent)

@@ -146,6 +146,10 @@ static uint32_t g_dense_trim = 0;
 // fltee_set_dense_trim_select: a trimmed call with t > FLTEE_TRIM_MAX is answered by selection
 // (k_trim_select.hip) instead of refused; t <= FLTEE_TRIM_MAX stays on the list kernel
 static bool g_dense_trim_select = false;
+// Multi-Krum (fltee_set_dense_krum): the assumed Byzantine clients f and the clients kept m of
+// every ECALL on the dense path; (0, 0) (default): off
+static uint32_t g_dense_krum_f = 0, g_dense_krum_m = 0;
+static bool dense_krum_on() { return (g_dense_krum_f | g_dense_krum_m) != 0; }
 
 // The trim count (include/fltee_agg.h fltee_trim_count): the one place it is decided.
 static size_t trim_count(size_t n, uint32_t per_mille) {
@@ -379,9 +383,9 @@ static bool ecall_takes_tree(uint32_t alg, size_t n, size_t rpc, size_t d) {
 // rpc: the records per client the aggregate sees (a packed, bf16 or fp8 call: d); fmt: c->records
 // holds value-only slices — FLTEE_OPT_PACKED, FLTEE_OPT_BF16 or FLTEE_OPT_FP8, 0 for records
 // trim: the call's trim count under fltee_set_dense_trim (0: an untrimmed call)
-static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d, size_t k_req,
+static EngineOpts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d, size_t k_req,
                                     size_t batch, uint64_t seed, uint32_t fmt = 0, size_t trim = 0) {
-    fltee_device_opts o;
+    EngineOpts o;
     std::memset(&o, 0, sizeof o);
     o.k_req = k_req;
     o.flags |= FLTEE_OPT_K_REQ;
@@ -393,6 +397,9 @@ static fltee_device_opts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d
     if (trim) o.flags |= FLTEE_OPT_TRIM, o.trim = trim;
     // (t past the lists reaches here only under fltee_set_dense_trim_select: refused before otherwise)
     if (trim > FLTEE_TRIM_MAX) o.flags |= FLTEE_OPT_TRIM_SELECT;
+    // (fltee_set_dense_krum: every call carries the flag, and the plan refuses what is not a dense
+    // call of a flat alg with n >= 2 f + 3, m <= n - f — never a plain mean)
+    if (dense_krum_on()) o.flags |= FLTEE_OPT_KRUM, o.krum_f = g_dense_krum_f, o.krum_m = g_dense_krum_m;
     if (ecall_takes_tree(alg, n, rpc, d)) o.flags |= FLTEE_OPT_ORAM_TREE;
     if (alg == FLTEE_ALG_NIPS19) o.seed = seed ? seed : next_seed();
     // advanced's fold (advanced.rs:66-101) runs once with halo = n: bit for bit for every
@@ -436,7 +443,7 @@ static uint32_t status_to_retval(uint32_t dev_st, uint32_t alg, bool *retry) {
 static uint32_t aggregate_records(DeviceCtx *c, uint32_t alg, size_t n, size_t rpc, size_t d,
                                   size_t k_req, size_t batch, float *d_out, uint64_t seed = 0,
                                   const void *rec = nullptr, uint32_t fmt = 0, size_t trim = 0) {
-    fltee_device_opts o = ecall_opts(alg, n, rpc, d, k_req, batch, seed, fmt, trim);
+    EngineOpts o = ecall_opts(alg, n, rpc, d, k_req, batch, seed, fmt, trim);
     if (alg == FLTEE_ALG_OPTIMIZED) o.flags &= ~FLTEE_OPT_K_REQ;
     if (!rec) rec = c->records.ptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -448,8 +455,8 @@ static uint32_t aggregate_records(DeviceCtx *c, uint32_t alg, size_t n, size_t r
         bool retry = false;
         st = status_to_retval(dev_st, alg, &retry);
         if (!retry) return st;
-        // (under fltee_set_dense_trim a sparse rerun would be an untrimmed mean: refused)
-        if (g_dense_trim) return FLTEE_ERROR_INVALID_PARAMETER;
+        // (under fltee_set_dense_trim / _krum a sparse rerun would be a plain mean: refused)
+        if (g_dense_trim || dense_krum_on()) return FLTEE_ERROR_INVALID_PARAMETER;
         o.flags &= ~FLTEE_OPT_DENSE;  // the sparse path: exact for any upload
     }
     return FLTEE_ERROR_INVALID_PARAMETER;
@@ -552,7 +559,7 @@ static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, si
         (!zero_copy && fl_memcpy_async(stage + d4 + 16, enc, cb, hipMemcpyHostToDevice, s) != hipSuccess) ||
         (!cb && fl_memset_async(d_st, 0, 4, s) != hipSuccess))
         return FLTEE_ERROR_UNEXPECTED;
-    fltee_device_opts o = ecall_opts(alg == FLTEE_ALG_OPTIMIZED ? FLTEE_ALG_ADVANCED : alg, n, rpa, d,
+    EngineOpts o = ecall_opts(alg == FLTEE_ALG_OPTIMIZED ? FLTEE_ALG_ADVANCED : alg, n, rpa, d,
                                      k_req, batch, seed, fmt, trim);
     if (alg == FLTEE_ALG_OPTIMIZED) o.flags &= ~FLTEE_OPT_K_REQ;
     // the call's device work: AES (timed by events) -> aggregation (-> DP) -> copy-out
@@ -566,7 +573,8 @@ static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, si
             return FLTEE_ERROR_UNEXPECTED;
         const uint32_t a = aggregate(alg, c->records.ptr, n, rpa, d, d_out, o, s, d_st);
         if (a != FLTEE_SUCCESS) return a;
-        if (cfg.dp && launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n - 2 * trim, next_seed(), s) != hipSuccess)
+        if (cfg.dp && launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, dense_krum_on() ? g_dense_krum_m : n - 2 * trim,
+                                      next_seed(), s) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
         return launch_copy_out(d_out, c->pin_out.dptr, d4 + 16, s) == hipSuccess
                    ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
@@ -584,8 +592,8 @@ static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, si
         st = status_to_retval(*(const volatile uint32_t *)((const uint8_t *)c->pin_out.ptr + d4), alg,
                               &retry);
         if (!retry) break;
-        // (under fltee_set_dense_trim a sparse rerun would be an untrimmed mean: refused)
-        if (g_dense_trim) return FLTEE_ERROR_INVALID_PARAMETER;
+        // (under fltee_set_dense_trim / _krum a sparse rerun would be a plain mean: refused)
+        if (g_dense_trim || dense_krum_on()) return FLTEE_ERROR_INVALID_PARAMETER;
         o.flags &= ~FLTEE_OPT_DENSE;  // the sparse path: exact for any upload
     }
     if (st) return st;
@@ -793,6 +801,14 @@ extern "C" fltee_status_t ecall_secure_aggregation(
                     (trim_count(n, trim_pm) > FLTEE_TRIM_MAX &&
                      (!g_dense_trim_select || n > FLTEE_TRIM_SELECT_MAX_N))))
         return fail(FLTEE_ERROR_INVALID_PARAMETER);
+    // Multi-Krum (fltee_set_dense_krum): likewise only a call on the dense path, never together
+    // with the trim, and never a plain mean — evaluated on the request as sent (n' <= n keeps no
+    // more); what depends on n' is the plan's refusal of the aggregate call itself
+    const bool krum_on = dense_krum_on();
+    if (krum_on && (!flat || !(fmt || rpc == d) || (aggregation_alg == FLTEE_ALG_PATH_ORAM && oram_tree_default()) ||
+                    trim_pm || n > FLTEE_KRUM_MAX_N || n < 2 * (size_t)g_dense_krum_f + 3 || g_dense_krum_m == 0 ||
+                    g_dense_krum_m > n - g_dense_krum_f))
+        return fail(FLTEE_ERROR_INVALID_PARAMETER);
 
     if (!c->outbuf.reserve(d * 4 + 16)) return fail(FLTEE_ERROR_OUT_OF_MEMORY);
     float *d_out = (float *)c->outbuf.ptr;
@@ -823,7 +839,8 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     // (a packed, bf16 or fp8 call is loaded on the root: the dense group path shards records by column;
     // a trimmed call too — it needs every client's value of a column in one place, which a
     // column shard has, but the group's per-rank sums are untrimmed: the root runs it)
-    if (G && flat && !tree && !fmt && !trim_pm && rpc == d && bpc == d * 8 + tagb) {
+    // (a Multi-Krum call likewise: the selection needs whole clients)
+    if (G && flat && !tree && !fmt && !trim_pm && !krum_on && rpc == d && bpc == d * 8 + tagb) {
         // dense uploads over a multi-GPU eid: every GPU loads and decrypts its own
         // parameter range (group.hip); "Loading" = the parallel H2D, "Decryption" = the
         // decrypt + aggregate + gather.  Authenticated: every GPU also hashes its range, the
@@ -937,7 +954,9 @@ extern "C" fltee_status_t ecall_secure_aggregation(
                                    trim_count(n_agg, trim_pm));
     }
     if (!st && cfg.dp) {  // lib.rs:399-408 (a trimmed call: the n' - 2 t clients it averaged)
-        if (launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping, n_agg - 2 * trim_count(n_agg, trim_pm), next_seed(),
+        // (a Multi-Krum call: the m clients it averaged)
+        if (launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping,
+                            krum_on ? g_dense_krum_m : n_agg - 2 * trim_count(n_agg, trim_pm), next_seed(),
                             c->stream) != hipSuccess)
             st = FLTEE_ERROR_UNEXPECTED;
     }
@@ -985,8 +1004,9 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
     if (uint32_t st = check_uploaded(cfg, client_ids, n)) return fail(st);
     for (size_t i = 0; i < n; ++i)
         if (!g_keys.count(client_ids[i])) return fail(FLTEE_ERROR_UNEXPECTED);
-    // (fltee_set_dense_trim: alg 6 is sort-based and cannot be trimmed — never an untrimmed mean)
-    if (g_dense_trim) return fail(FLTEE_ERROR_INVALID_PARAMETER);
+    // (fltee_set_dense_trim / _krum: alg 6 is sort-based and cannot be trimmed or scored — never a
+    // plain mean)
+    if (g_dense_trim || dense_krum_on()) return fail(FLTEE_ERROR_INVALID_PARAMETER);
 
     const bool aead = g_upload_aead;
     if (aead && !gcm_sizes_ok(k * 8, 16)) return fail(FLTEE_ERROR_INVALID_PARAMETER);
@@ -1316,6 +1336,11 @@ extern "C" size_t fltee_trim_count(size_t n, uint32_t per_mille) { return trim_c
 extern "C" void fltee_set_dense_trim_select(int on) {
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
     g_dense_trim_select = on != 0;
+}
+
+extern "C" void fltee_set_dense_krum(uint32_t f, uint32_t m) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    g_dense_krum_f = f, g_dense_krum_m = m;
 }
 
 extern "C" void fltee_set_dense_trim(uint32_t per_mille) {

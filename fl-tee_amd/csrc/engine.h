@@ -52,6 +52,8 @@ enum Route : uint32_t {
     kRouteTrimSelectDense,   // FLTEE_OPT_TRIM | _TRIM_SELECT with t > 0 on records: trim by selection (k_trim_select.hip)
     kRouteTrimSelectPacked,  // ... on packed rows
     kRouteFp8,           // flat algs, FLTEE_OPT_FP8: the fp8 accumulate (k_rows.hip)
+    kRouteKrumDense,     // flat algs, FLTEE_OPT_KRUM on records: Multi-Krum (k_krum.hip; its scratch in ws_mat)
+    kRouteKrumPacked,    // ... on packed rows
 };
 enum Tail : uint32_t {
     kTailNone,
@@ -69,6 +71,12 @@ struct AdvShape {
     Tail tail = kTailNone;
     bool stable = false;  // alg 7: the first sort is the stable network's (k_stable.hip)
     size_t side_bytes = 0, lb_bytes = 0;
+};
+
+// A call's options as the engine holds them: the public struct, and behind it the fields of
+// fltee_device_opts_krum (read_opts fills them under FLTEE_OPT_KRUM; zero otherwise).
+struct EngineOpts : fltee_device_opts {
+    size_t krum_f, krum_m;
 };
 
 // The one decision about a call's public shape (alg, n, k, d, opts): whether it is refused,
@@ -150,7 +158,11 @@ void set_bubble_ecall(int on);
 bool bubble_ecall_default();
 
 fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size_t d, float *out,
-                         const fltee_device_opts &o, hipStream_t s, uint32_t *status);
+                         const EngineOpts &o, hipStream_t s, uint32_t *status);
+// a FLTEE_OPT_KRUM call up to its selection: the n scores and keep words copied to sel_scores /
+// sel_keep (device memory), nothing written to an output
+fltee_status_t krum_select(const void *rec, size_t n, size_t d, const EngineOpts &o, double *sel_scores,
+                           uint32_t *sel_keep, hipStream_t s, uint32_t *status);
 // common.rs:25-35 on m entries of src (the shuffled array), bit-exact: out[i] = coef *
 // (+0 + v1 + v2 ...) over the entries with idx == i in position order (accumulate:
 // out[i] += the un-scaled sum).  Synchronises `s` once to read the selected count.
@@ -164,9 +176,9 @@ hipError_t ordered_from_list(DeviceCtx *c, const uint64_t *sel, size_t lc, size_
 hipError_t advanced_batch(const void *rec, size_t n, size_t k, size_t d, size_t halo, float *out,
                           uint32_t *status, hipStream_t s);
 hipError_t read_device_word(DeviceCtx *c, const uint32_t *dev_word, size_t *out, hipStream_t s);
-size_t workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o);
-bool reserve(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o);
+size_t workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpts &o);
+bool reserve(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpts &o);
 // the plan's refusal alone (host arithmetic)
-fltee_status_t plan_status(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o);
+fltee_status_t plan_status(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpts &o);
 
 }  // namespace fltee

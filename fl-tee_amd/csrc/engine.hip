@@ -247,7 +247,7 @@ static bool one_row_flag(uint32_t flags) {
     return (f & (f - 1)) == 0;
 }
 
-static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
+static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpts &o) {
     Plan p;
     // a value-row upload is a dense one: n rows of values, k == d >= rows_min_d (f32: 2, bf16: 3,
     // fp8: 13)
@@ -273,6 +273,15 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
                   2 * o.trim >= n);  // (o.trim >= n: 2 t may wrap)
     }
     refuse_if(select && !trim);
+    // Multi-Krum (FLTEE_OPT_KRUM, k_krum.hip): a dense call on the flat algs without the tree,
+    // n >= 2 f + 3, 1 <= m <= n - f, n <= FLTEE_KRUM_MAX_N; never together with the trim
+    const bool krum = (o.flags & FLTEE_OPT_KRUM) != 0;
+    if (krum) {
+        const bool flat = alg == FLTEE_ALG_BASELINE || alg == FLTEE_ALG_NON_OBLIVIOUS || alg == FLTEE_ALG_PATH_ORAM;
+        refuse_if(!flat || !dense || trim || (o.flags & (FLTEE_OPT_ORAM_TREE | FLTEE_OPT_ORAM_LAZY)) ||
+                  n > FLTEE_KRUM_MAX_N || o.krum_f > n || n < 2 * o.krum_f + 3 ||  // (f > n: 2 f may wrap)
+                  o.krum_m == 0 || o.krum_m > n - o.krum_f);
+    }
     switch (alg) {
     case FLTEE_ALG_PATH_ORAM:
     case FLTEE_ALG_BASELINE:
@@ -296,6 +305,12 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
             if (trim && o.trim)
                 p.route = select ? (packed ? kRouteTrimSelectPacked : kRouteTrimSelectDense)
                                  : (packed ? kRouteTrimPacked : kRouteTrimDense);
+            // (a bf16 or fp8 Krum call: the records route on the unpacked copy, as for the trim)
+            if (krum) {
+                p.route = packed ? kRouteKrumPacked : kRouteKrumDense;
+                // the Gram partials, G, the scores and the keep words: a slot no dense route touches
+                p.bytes[kWsMat] = n <= FLTEE_KRUM_MAX_N ? krum_scratch_bytes(n, d) : 0;
+            }
         } else if (alg == FLTEE_ALG_NON_OBLIVIOUS && use_scatter_rows(n, k, d)) {
             p.route = kRouteScatterRows;
             p.bytes[kWsMat] = n * d * 4;
@@ -357,13 +372,14 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const fltee_dev
         p.bytes[kWsCoef] = n * 4;
         p.clip_records = p.route != kRouteDense && p.route != kRoutePacked && p.route != kRouteTrimDense &&
                          p.route != kRouteTrimPacked && p.route != kRouteBf16 && p.route != kRouteFp8 &&
-                         p.route != kRouteTrimSelectDense && p.route != kRouteTrimSelectPacked;
+                         p.route != kRouteTrimSelectDense && p.route != kRouteTrimSelectPacked &&
+                         p.route != kRouteKrumDense && p.route != kRouteKrumPacked;
         if (p.clip_records) p.bytes[kWsRec] = nrec * 8;
     }
     // every route but the packed / bf16 / fp8 accumulate reads records: the plan (n, d, d) has, on the
     // rows unpacked into the record scratch (where FLTEE_OPT_CLIP then clips them in place)
     p.unpack = fmt != kRowsNone && p.route != kRoutePacked && p.route != kRouteTrimPacked && p.route != kRouteBf16 &&
-               p.route != kRouteTrimSelectPacked && p.route != kRouteFp8;
+               p.route != kRouteTrimSelectPacked && p.route != kRouteFp8 && p.route != kRouteKrumPacked;
     if (p.unpack) p.bytes[kWsRec] = nrec * 8;
     return p;
 }
@@ -566,7 +582,7 @@ hipError_t advanced_batch(const void *rec, size_t n, size_t k, size_t d, size_t 
                           uint32_t *status, hipStream_t s) {
     DeviceCtx *c = current_ctx();
     if (!c) return hipErrorInvalidDevice;
-    fltee_device_opts o;
+    EngineOpts o;
     std::memset(&o, 0, sizeof o);
     o.fold_halo = halo;
     const Plan p = plan_for(FLTEE_ALG_ADVANCED, n, k, d, o);
@@ -576,8 +592,11 @@ hipError_t advanced_batch(const void *rec, size_t n, size_t k, size_t d, size_t 
 }
 
 // plan -> the refusal -> the plan's scratch -> clip -> the route -> DP
-fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size_t d, float *out,
-                         const fltee_device_opts &o, hipStream_t s, uint32_t *status) {
+// sel_scores / sel_keep (krum_select): a Multi-Krum call ends after its selection, the scores and
+// keep words copied there
+static fltee_status_t aggregate_impl(uint32_t alg, const void *rec, size_t n, size_t k, size_t d, float *out,
+                                     const EngineOpts &o, hipStream_t s, uint32_t *status,
+                                     double *sel_scores, uint32_t *sel_keep) {
     DeviceCtx *c = current_ctx();
     if (!c) return FLTEE_ERROR_UNEXPECTED;
     const Plan p = plan_for(alg, n, k, d, o);
@@ -585,7 +604,11 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     if (!reserve_plan(c, p, &s)) return FLTEE_ERROR_OUT_OF_MEMORY;
     const bool acc = (o.flags & FLTEE_OPT_ACCUMULATE) != 0;
     // (the trimmed mean averages the n - 2 t clients it keeps; the DP noise takes the same divisor)
-    const size_t n_avg = o.n_avg ? o.n_avg : (o.flags & FLTEE_OPT_TRIM) ? n - 2 * o.trim : n;
+    // (Multi-Krum averages the m clients it keeps)
+    const size_t n_avg = o.n_avg                        ? o.n_avg
+                         : (o.flags & FLTEE_OPT_TRIM) ? n - 2 * o.trim
+                         : (o.flags & FLTEE_OPT_KRUM) ? o.krum_m
+                                                      : n;
     const float coef = (o.flags & FLTEE_OPT_NO_AVERAGE) ? 1.0f : 1.0f / (float)n_avg;
 
     // packed / bf16 / fp8 rows off their own route: every alg below runs on the records (j, v[j])
@@ -648,6 +671,21 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
         e = launch_trim_select(rec, p.route == kRouteTrimSelectPacked, n, d, o.trim, coef, out, ccoef, acc, status,
                                s);
         break;
+    case kRouteKrumDense:
+    case kRouteKrumPacked: {
+        const bool rows = p.route == kRouteKrumPacked;
+        c->mat_clean = 0;  // (the scatter rows' sentinel, if it was there, is overwritten)
+        e = launch_krum_select(rec, rows, n, d, o.krum_f, o.krum_m, ccoef, c->ws_mat.ptr, status, s);
+        if (e == hipSuccess && sel_scores) {
+            e = fl_memcpy_async(sel_scores, krum_scores(c->ws_mat.ptr, n, d), n * 8, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess)
+                e = fl_memcpy_async(sel_keep, krum_keep(c->ws_mat.ptr, n, d), n * 4, hipMemcpyDeviceToDevice, s);
+            return e == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+        }
+        if (e == hipSuccess)
+            e = launch_krum_accumulate(rec, rows, n, d, krum_keep(c->ws_mat.ptr, n, d), coef, out, ccoef, acc, s);
+        break;
+    }
     case kRouteScatterRows:
         if (c->mat_clean_ptr != c->ws_mat.ptr || c->mat_clean_cap != c->ws_mat.cap) {
             c->mat_clean = 0;  // a new allocation: contents unknown
@@ -723,24 +761,35 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
     return e == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
 }
 
-size_t workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
+fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size_t d, float *out,
+                         const EngineOpts &o, hipStream_t s, uint32_t *status) {
+    return aggregate_impl(alg, rec, n, k, d, out, o, s, status, nullptr, nullptr);
+}
+
+fltee_status_t krum_select(const void *rec, size_t n, size_t d, const EngineOpts &o, double *sel_scores,
+                           uint32_t *sel_keep, hipStream_t s, uint32_t *status) {
+    if (!(o.flags & FLTEE_OPT_KRUM) || !sel_scores || !sel_keep) return FLTEE_ERROR_INVALID_PARAMETER;
+    return aggregate_impl(FLTEE_ALG_BASELINE, rec, n, d, d, nullptr, o, s, status, sel_scores, sel_keep);
+}
+
+size_t workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpts &o) {
     const Plan p = plan_for(alg, n, k, d, o);
     size_t sum = 0;
     for (size_t b : p.bytes) sum += b;
     return sum;
 }
 
-fltee_status_t plan_status(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
+fltee_status_t plan_status(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpts &o) {
     return plan_for(alg, n, k, d, o).status;
 }
 
-bool reserve(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o) {
+bool reserve(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpts &o) {
     DeviceCtx *c = current_ctx();
     return c && reserve_plan(c, plan_for(alg, n, k, d, o), nullptr);
 }
 
 // fltee_debug_plan: the plan as words (host only, no device needed)
-fltee_status_t debug_plan_words(uint32_t alg, size_t n, size_t k, size_t d, const fltee_device_opts &o,
+fltee_status_t debug_plan_words(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpts &o,
                                 uint64_t *out) {
     const Plan p = plan_for(alg, n, k, d, o);
     out[0] = p.route, out[1] = p.adv.tail;
@@ -766,20 +815,25 @@ void release_scratch() {
 // ============================================================ C ABI =========
 using namespace fltee;
 
-static fltee_device_opts default_opts() {
-    fltee_device_opts o;
+static EngineOpts default_opts() {
+    EngineOpts o;
     std::memset(&o, 0, sizeof o);
     return o;
 }
 
-// The caller's options.  `trim`, the struct's last field, is read only under FLTEE_OPT_TRIM:
-// a caller built against the struct that ended at d_status never sets the flag, and nothing
-// past its struct is touched.
-static fltee_device_opts read_opts(const fltee_device_opts *opts) {
-    fltee_device_opts o = default_opts();
+// The caller's options.  The struct is copied up to `trim`; each field from there on is read
+// only under its own flag (trim: FLTEE_OPT_TRIM; krum_f, krum_m, which lie behind the struct in a
+// fltee_device_opts_krum: FLTEE_OPT_KRUM): a caller built against a struct that ended earlier
+// never sets the flag, and nothing past its struct is touched.
+static EngineOpts read_opts(const fltee_device_opts *opts) {
+    EngineOpts o = default_opts();
     if (!opts) return o;
-    std::memcpy(&o, opts, offsetof(fltee_device_opts, trim));
+    std::memcpy(static_cast<fltee_device_opts *>(&o), opts, offsetof(fltee_device_opts, trim));
     if (o.flags & FLTEE_OPT_TRIM) o.trim = opts->trim;
+    if (o.flags & FLTEE_OPT_KRUM) {
+        const fltee_device_opts_krum *k = reinterpret_cast<const fltee_device_opts_krum *>(opts);
+        o.krum_f = k->krum_f, o.krum_m = k->krum_m;
+    }
     return o;
 }
 
@@ -787,7 +841,7 @@ extern "C" fltee_status_t fltee_aggregate_device(uint32_t alg, const void *d_rec
                                                  size_t k, size_t d, float *d_out,
                                                  const fltee_device_opts *opts, void *stream) {
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
-    const fltee_device_opts o = read_opts(opts);
+    const EngineOpts o = read_opts(opts);
     // (bf16 rows are read as 2-byte halves: an odd base is refused by host arithmetic)
     if ((o.flags & FLTEE_OPT_BF16) && ((uintptr_t)d_records & 1)) return FLTEE_ERROR_INVALID_PARAMETER;
     // (fp8 rows carry an f32 scale, read as one: a base that is not 4-byte aligned likewise)
@@ -800,18 +854,43 @@ extern "C" fltee_status_t fltee_aggregate_device(uint32_t alg, const void *d_rec
     return aggregate(alg, d_records, n, k, d, d_out, o, s, status);
 }
 
+extern "C" fltee_status_t fltee_krum_select_device(const void *d_records, size_t n, size_t d,
+                                                   const fltee_device_opts *opts, double *d_scores,
+                                                   uint32_t *d_keep, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    // (the flag is the caller's word that opts is the base of a fltee_device_opts_krum)
+    if (!opts || !(opts->flags & FLTEE_OPT_KRUM) || !d_scores || !d_keep) return FLTEE_ERROR_INVALID_PARAMETER;
+    // steps 1 - 4 take the layout, the clip and (f, m) from the options and nothing else
+    const EngineOpts in = read_opts(opts);
+    EngineOpts o = default_opts();
+    o.flags = (in.flags & (FLTEE_OPT_PACKED | FLTEE_OPT_BF16 | FLTEE_OPT_FP8 | FLTEE_OPT_CLIP)) | FLTEE_OPT_DENSE |
+              FLTEE_OPT_KRUM;
+    o.clipping = in.clipping, o.d_status = in.d_status;
+    o.krum_f = in.krum_f, o.krum_m = in.krum_m;
+    if ((o.flags & FLTEE_OPT_BF16) && ((uintptr_t)d_records & 1)) return FLTEE_ERROR_INVALID_PARAMETER;
+    if ((o.flags & FLTEE_OPT_FP8) && ((uintptr_t)d_records & 3)) return FLTEE_ERROR_INVALID_PARAMETER;
+    if (plan_status(FLTEE_ALG_BASELINE, n, d, d, o) != FLTEE_SUCCESS) return FLTEE_ERROR_INVALID_PARAMETER;
+    DeviceCtx *c = current_ctx();
+    if (!c) return FLTEE_ERROR_UNEXPECTED;
+    uint32_t *status = o.d_status ? o.d_status : c->status;
+    hipStream_t s = (hipStream_t)stream;
+    if (!o.d_status && fl_memset_async(c->status, 0, 4, s) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+    return krum_select(d_records, n, d, o, d_scores, d_keep, s, status);
+}
+
 extern "C" size_t fltee_workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d,
                                         const fltee_device_opts *opts) {
-    const fltee_device_opts o = read_opts(opts);
+    const EngineOpts o = read_opts(opts);
     return workspace_bytes(alg, n, k, d, o);
 }
 
 extern "C" fltee_status_t fltee_reserve(uint32_t alg, size_t n, size_t k, size_t d,
                                         const fltee_device_opts *opts) {
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
-    const fltee_device_opts o = read_opts(opts);
+    const EngineOpts o = read_opts(opts);
     // a refused trimmed call is refused here too, by the plan, before anything is reserved
-    if ((o.flags & (FLTEE_OPT_TRIM | FLTEE_OPT_TRIM_SELECT)) && plan_status(alg, n, k, d, o) != FLTEE_SUCCESS)
+    if ((o.flags & (FLTEE_OPT_TRIM | FLTEE_OPT_TRIM_SELECT | FLTEE_OPT_KRUM)) &&
+        plan_status(alg, n, k, d, o) != FLTEE_SUCCESS)
         return FLTEE_ERROR_INVALID_PARAMETER;
     return reserve(alg, n, k, d, o) ? FLTEE_SUCCESS : FLTEE_ERROR_OUT_OF_MEMORY;
 }
@@ -1373,6 +1452,13 @@ extern "C" void fltee_debug_set_fused_init(int on) { fltee::set_fused_init(on); 
 extern "C" fltee_status_t fltee_debug_plan(uint32_t alg, size_t n, size_t k, size_t d,
                                            const fltee_device_opts *opts, uint64_t *out) {
     return fltee::debug_plan_words(alg, n, k, d, read_opts(opts), out);
+}
+// test hook: the Gram pass's geometry for (n, d) (k_krum.hip krum_geometry), host only:
+// {padded rows, 16-row tiles, 128-row macro-tiles, columns a chunk, chunks, scratch bytes}
+extern "C" void fltee_debug_krum_geometry(size_t n, size_t d, uint64_t *out) {
+    const fltee::KrumGeom g = fltee::krum_geometry(n, d);
+    out[0] = g.np, out[1] = g.tiles, out[2] = g.macros, out[3] = g.chunk_cols, out[4] = g.chunks;
+    out[5] = fltee::krum_scratch_bytes(n, d);
 }
 // test hooks: which engine scratch buffers grew (allocated) since the last call — bit w for
 // buffer w in Ws order — read and cleared; and the current device's engine scratch released

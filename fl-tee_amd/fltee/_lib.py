@@ -56,6 +56,8 @@ OPT_FP8 = 0x1000  # d_records: fp8 dense slices (8 * (ceil(d / 8) + 1) bytes: e4
 AAD_FP8_BIT = 0x20000000  # FLTEE_AAD_FP8_BIT: an fp8 call's last AAD word is alg | this
 OPT_TRIM_SELECT = 0x800  # with OPT_TRIM: trim by selection (k_trim_select.hip), any trim with 2 * trim < n
 TRIM_SELECT_MAX_N = 4096  # FLTEE_TRIM_SELECT_MAX_N
+OPT_KRUM = 0x2000  # Multi-Krum of a dense call (k_krum.hip): DeviceOptsKrum.krum_f assumed Byzantine, krum_m kept
+KRUM_MAX_N = 1024  # FLTEE_KRUM_MAX_N
 
 
 class DeviceOpts(ctypes.Structure):
@@ -71,6 +73,15 @@ class DeviceOpts(ctypes.Structure):
         ("fold_halo", ctypes.c_size_t),
         ("d_status", ctypes.c_void_p),
         ("trim", ctypes.c_size_t),
+    ]
+
+
+class DeviceOptsKrum(DeviceOpts):
+    """struct fltee_device_opts_krum: the options of an OPT_KRUM call, DeviceOpts with Multi-Krum's
+    two counts behind it (passed wherever a DeviceOpts pointer is taken; read under the flag)."""
+    _fields_ = [
+        ("krum_f", ctypes.c_size_t),
+        ("krum_m", ctypes.c_size_t),
     ]
 
 
@@ -106,6 +117,8 @@ SIGNATURES = {
     "fltee_trim_count": (_S, [_S, _U32]),
     "fltee_set_dense_trim": (None, [_U32]),
     "fltee_set_dense_trim_select": (None, [ctypes.c_int]),
+    "fltee_krum_select_device": (_U32, [_P, _S, _S, ctypes.POINTER(DeviceOpts), _P, _P, _P]),
+    "fltee_set_dense_krum": (None, [_U32, _U32]),
     "fltee_bf16_slice_bytes": (_S, [_S]),
     "fltee_upload_is_bf16": (ctypes.c_int, [ctypes.c_int, _S, _S, _S]),
     "fltee_set_upload_bf16": (None, [ctypes.c_int]),
@@ -184,6 +197,7 @@ EXTRA_SIGNATURES = {  # test hooks not in the public header
     "fltee_debug_fold_geometry": (None, [_S, _S, _S, _S, _P]),
     "fltee_debug_plan": (_U32, [_U32, _S, _S, _S, ctypes.POINTER(DeviceOpts), _P]),
     "fltee_debug_scratch_grown": (_U32, []),
+    "fltee_debug_krum_geometry": (None, [_S, _S, _P]),
     "fltee_debug_scratch_release": (None, []),
     "fltee_debug_set_pad_skip": (None, [ctypes.c_int]),
     "fltee_debug_set_radix_order": (None, [ctypes.c_int]),

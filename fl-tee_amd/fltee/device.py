@@ -39,8 +39,8 @@ def unpack_records(rec):
 def opts(*, dense=False, dp=False, clip=False, accumulate=False, no_average=False, sigma=1.12,
          clipping=1.0, seed=0, k_req=None, batch=0, n_avg=0, fold_halo=0, status=None,
          oram_tree=False, oram_lazy=False, packed=False, trim=None, bf16=False, trim_select=False,
-         fp8=False):
-    o = L.DeviceOpts()
+         fp8=False, krum=None):
+    o = L.DeviceOptsKrum() if krum is not None else L.DeviceOpts()
     o.flags = ((L.OPT_DENSE if dense else 0) | (L.OPT_DP if dp else 0) | (L.OPT_CLIP if clip else 0)
                | (L.OPT_ACCUMULATE if accumulate else 0) | (L.OPT_NO_AVERAGE if no_average else 0)
                | (L.OPT_ORAM_TREE if oram_tree else 0) | (L.OPT_ORAM_LAZY if oram_lazy else 0)
@@ -55,6 +55,9 @@ def opts(*, dense=False, dp=False, clip=False, accumulate=False, no_average=Fals
         o.trim = trim
     if trim_select:  # ... by selection: any trim with 2 * trim < n, n <= TRIM_SELECT_MAX_N
         o.flags |= L.OPT_TRIM_SELECT
+    if krum is not None:  # Multi-Krum of a dense call: (f assumed Byzantine clients, m clients kept)
+        o.flags |= L.OPT_KRUM
+        o.krum_f, o.krum_m = krum
     o.d_status = status.data_ptr() if status is not None else None
     return o
 
@@ -69,7 +72,9 @@ def aggregate(alg, records, n, k, d, out=None, stream=None, **kw):
     packed=True: records is n packed slices instead (any cuda tensor of n * packed_row(d)
     f32's worth of bytes: client c's d values, then one ignored f32 when d is odd; k == d).
     bf16=True: n bf16 slices (n * bf16_row(d) halves' worth of bytes, 2-byte aligned).
-    fp8=True: n fp8 slices (n * fp8_row(d) bytes, 4-byte aligned)."""
+    fp8=True: n fp8 slices (n * fp8_row(d) bytes, 4-byte aligned).
+    krum=(f, m): Multi-Krum of a dense call on algs 3, 4, 5 — the m clients with the smallest sums
+    of squared distances to their n - f - 2 nearest neighbours, averaged whole."""
     if kw.get("fp8"):
         assert records.is_cuda and records.numel() * records.element_size() >= n * fp8_row(d)
     elif kw.get("bf16"):
@@ -85,6 +90,19 @@ def aggregate(alg, records, n, k, d, out=None, stream=None, **kw):
                                         _stream(stream))
     _check(st, "fltee_aggregate_device")
     return out
+
+
+def krum_select(records, n, d, f, m, stream=None, **kw):
+    """fltee_krum_select_device: Multi-Krum's scores and selection alone, on n dense uploads of
+    d parameters (records, or packed= / bf16= / fp8= rows; clip= with clipping=) ->
+    (scores float64 [n], keep int32 [n]: 0 or -1), cuda tensors."""
+    assert records.is_cuda
+    o = opts(krum=(f, m), **kw)
+    scores = torch.empty(n, dtype=torch.float64, device=records.device)
+    keep = torch.empty(n, dtype=torch.int32, device=records.device)
+    _check(L.lib().fltee_krum_select_device(_ptr(records), n, d, ctypes.byref(o), _ptr(scores), _ptr(keep),
+                                            _stream(stream)), "fltee_krum_select_device")
+    return scores, keep
 
 
 def packed_row(d):

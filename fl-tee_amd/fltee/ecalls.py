@@ -108,6 +108,10 @@ class Enclave:
         """fltee_set_dense_trim (process-wide; see the module function of the same name)."""
         set_dense_trim(per_mille)
 
+    def set_dense_krum(self, f, m):
+        """fltee_set_dense_krum (process-wide; see the module function of the same name)."""
+        set_dense_krum(f, m)
+
     def set_dense_trim_select(self, on):
         """fltee_set_dense_trim_select (process-wide; see the module function of the same name)."""
         set_dense_trim_select(on)
@@ -180,6 +184,19 @@ def set_dense_trim_select(on):
     by the selection kernel for up to TRIM_SELECT_MAX_N clients instead of ending with 0x2; a
     call with a trim count up to TRIM_MAX runs as before."""
     L.lib().fltee_set_dense_trim_select(1 if on else 0)
+
+
+def set_dense_krum(f, m):
+    """Multi-Krum (fltee_set_dense_krum; (0, 0), the default, is off): while on, a dense or packed
+    ecall_secure_aggregation call on algs 3, 4, 5 scores every client by the squared distances to
+    its n' - f - 2 nearest neighbours and returns the mean of the m best-scored clients, whole.
+    Every call that cannot be answered so (algs 1, 2, 6, 7, a sparse upload, the tree,
+    n' < 2 f + 3, m > n' - f, more than KRUM_MAX_N clients, set_dense_trim on as well) ends with
+    retval 0x2, never with a plain mean."""
+    f, m = int(f), int(m)
+    if f < 0 or m < 0 or f >= 2 ** 32 or m >= 2 ** 32:
+        raise ValueError(f"krum (f, m) = ({f}, {m}) is not a pair of u32")
+    L.lib().fltee_set_dense_krum(f, m)
 
 
 def trim_count(n, per_mille):

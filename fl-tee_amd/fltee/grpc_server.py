@@ -10,6 +10,7 @@ code); the handlers are fltee.server.Aggregator, the server.rs logic over the C 
                                 [--strict-reference] [--quiet]
                                 [--aead [--aead-policy abort|report|drop]]
                                 [--packed-dense] [--bf16-dense] [--fp8-dense] [--trim-per-mille N [--trim-select]]
+                                [--krum-f N --krum-m M]
 
 Like the reference: verbose on, dp off (server.rs:236-237; --dp turns DP on for
 the configs[3] runs), one enclave per process; calls are serialised by the
@@ -139,15 +140,27 @@ def main(argv=None):
     ap.add_argument("--trim-select", action="store_true",
                     help="with --trim-per-mille: answer requests that trim more than 64 clients a "
                          "side (up to 4096 clients) by the selection kernel instead of refusing them")
+    ap.add_argument("--krum-f", type=int, default=0, metavar="N",
+                    help="Multi-Krum of dense uploads (algs 3, 4, 5), with --krum-m: the assumed number "
+                         "of Byzantine clients (a request needs at least 2 N + 3 clients)")
+    ap.add_argument("--krum-m", type=int, default=0, metavar="M",
+                    help="Multi-Krum: the M best-scored clients are averaged whole (0 with --krum-f 0: "
+                         "off); requests that cannot be answered so are refused, and --trim-per-mille "
+                         "cannot be on at the same time")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
+    if (args.krum_f or args.krum_m) and args.trim_per_mille:
+        ap.error("--krum-f / --krum-m and --trim-per-mille are alternatives")
+    if args.krum_f < 0 or args.krum_m < 0 or (args.krum_f and not args.krum_m):
+        ap.error("--krum-f needs a positive --krum-m")
     if args.aead_policy is not None and not args.aead:
         ap.error("--aead-policy needs --aead")
     agg = Aggregator(device=args.device, verbose=not args.quiet, dp=args.dp,
                      strict_reference=args.strict_reference, aead=args.aead,
                      aead_policy=args.aead_policy or "abort", min_survivors=args.aead_min_survivors,
                      packed=args.packed_dense, trim_per_mille=args.trim_per_mille,
-                     bf16=args.bf16_dense, trim_select=args.trim_select, fp8=args.fp8_dense)
+                     bf16=args.bf16_dense, trim_select=args.trim_select, fp8=args.fp8_dense,
+                     krum=(args.krum_f, args.krum_m) if (args.krum_f or args.krum_m) else None)
     server, port = make_server(agg, args.address, verbose=not args.quiet)
     server.start()
     print(f"[Server] Now GRPC Server is binded on {args.address} (port {port})", flush=True)

@@ -41,12 +41,17 @@ request).  Documented deviations from the reference host:
   * `trim_select=True` (off by default) lets `trim_per_mille` trim more than 64 clients a side
     (the median from 131 clients on, up to 4096 clients): such a request is answered by the
     selection kernel instead of refused; requests that trim up to 64 run as before.
+  * `krum=(f, m)` (None, off, by default) answers dense uploads to algs 3, 4, 5 with Multi-Krum:
+    every client is scored by the squared distances to its n - f - 2 nearest neighbours and the
+    m best-scored clients are averaged whole.  An alternative to `trim_per_mille` (both on: every
+    request is refused); a request that cannot be answered so is a ServerPanic (retval 0x2),
+    never a plain mean.
 """
 import argparse
 import time
 
 from . import _lib as L
-from .ecalls import (AEAD_POLICIES, Enclave, set_dense_trim, set_dense_trim_select, set_upload_aead,
+from .ecalls import (AEAD_POLICIES, Enclave, set_dense_krum, set_dense_trim, set_dense_trim_select, set_upload_aead,
                      set_upload_aead_policy, set_upload_bf16, set_upload_fp8, set_upload_packed)
 
 
@@ -68,7 +73,7 @@ def per_mille(text):
 class Aggregator:
     def __init__(self, device=0, verbose=False, dp=False, strict_reference=False, enclave=None,
                  aead=False, aead_policy="abort", min_survivors=1, packed=False, trim_per_mille=0,
-                 bf16=False, trim_select=False, fp8=False):
+                 bf16=False, trim_select=False, fp8=False, krum=None):
         if aead_policy not in AEAD_POLICIES:
             raise ValueError(f"aead_policy must be one of {sorted(AEAD_POLICIES)}")
         if aead_policy != "abort" and not aead:
@@ -97,6 +102,9 @@ class Aggregator:
         self.trim_select = bool(trim_select)
         if self.trim_select:  # process-wide too
             set_dense_trim_select(True)
+        self.krum = tuple(int(v) for v in krum) if krum is not None else None
+        if self.krum is not None:  # process-wide too
+            set_dense_krum(*self.krum)
         self.verbose = verbose
         self.dp = dp
         self.strict_reference = strict_reference

@@ -295,6 +295,49 @@ fltee_status_t ecall_client_size_optimized_secure_aggregation(
                                       record scratch, exactly as a FLTEE_OPT_BF16 call does.
                                       d_records is never written.  DP, ACCUMULATE, NO_AVERAGE and
                                       n_avg mean what they mean on the dense route */
+#define FLTEE_OPT_KRUM 0x2000u     /* Multi-Krum (Blanchard et al., 2017) of a dense call
+                                      (k_krum.hip): algs 3, 4, 5 with FLTEE_OPT_DENSE or
+                                      FLTEE_OPT_PACKED, k = d; opts is a fltee_device_opts_krum
+                                      (below): f = krum_f assumed Byzantine clients, m = krum_m kept.  A FLTEE_OPT_BF16 / _FP8
+                                      call runs on its unpacked records, as a trimmed one does.  With
+                                      x_c[j] the value the dense route would add for client c at j
+                                      (FLTEE_OPT_CLIP: v * coef_c rounded):
+                                        1. G[a][b] = sum_j (f64)x_a[j] * (f64)x_b[j]: every product
+                                           exact, the sum in f64 in one order for every entry, a
+                                           function of (n, d) alone (f64 MFMA over column chunks, the
+                                           chunks' partials added in ascending order; no atomics):
+                                           identical rows have identical entries, and a call repeats
+                                           its bits;
+                                        2. D[a][b] = (G[a][a] + G[b][b]) - 2 G[a][b] in f64, in that
+                                           association; NaN and +-inf count as +inf, anything not
+                                           above 0 as +0.0 (two identical rows: exactly 0);
+                                        3. s_a = the f64 sum of the q = n - f - 2 smallest D[a][b],
+                                           b != a, added in ascending order from +0.0;
+                                        4. kept: the m clients smallest by (s ascending, client
+                                           ascending); clients with s = +inf come last, in upload
+                                           order;
+                                        5. out[j] = sum * (1f32 / (f32)div), sum = the in-order f32 sum
+                                           ((+0.0 + x_c1) + x_c2) + ... of the kept clients in upload
+                                           order — a dropped client adds a selected +0.0, never a
+                                           product with 0: a dropped NaN reaches no sum — and
+                                           div = n_avg ? n_avg : m, which is the DP noise's divisor
+                                           too; ACCUMULATE, NO_AVERAGE and DP mean what they mean on
+                                           the dense route.  m = n - f with f = 0 keeps every client:
+                                           the dense route's result bit for bit.
+                                      Oblivious: every value is read at a fixed address (twice), the
+                                      sort and the ranking are networks of compares feeding selects,
+                                      the launch shapes depend on (n, d) and the pointers' alignment;
+                                      q and m are compare constants.  The keep set never leaves the
+                                      device.  Scratch: the Gram partials, G, the scores and the keep
+                                      words, sized from (n, d) (with FLTEE_OPT_CLIP the coefficients
+                                      too); the records layout raises FLTEE_DEV_ERR_DENSE_ORDER as
+                                      the dense route does.  Refused with INVALID_PARAMETER by host
+                                      arithmetic, before anything is reserved or launched:
+                                      n < 2 f + 3, m = 0, m > n - f, n > FLTEE_KRUM_MAX_N, any other
+                                      alg, a call that is not dense, FLTEE_OPT_ORAM_TREE / _LAZY, and
+                                      the flag together with FLTEE_OPT_TRIM (the two robust aggregates
+                                      are alternatives) */
+#define FLTEE_KRUM_MAX_N 1024
 
 typedef struct fltee_device_opts {
     uint32_t flags;     /* FLTEE_OPT_* */
@@ -313,6 +356,19 @@ typedef struct fltee_device_opts {
                            last field, read only when the flag is set: a caller built against the
                            struct without it, which never sets the flag, is unaffected */
 } fltee_device_opts;
+
+/* The options of a FLTEE_OPT_KRUM call: fltee_device_opts with Multi-Krum's two counts behind
+ * `trim`.  A caller that sets FLTEE_OPT_KRUM in base.flags passes &x.base wherever a
+ * const fltee_device_opts * is taken, and vouches by the flag that the two fields lie behind it:
+ * the library copies a caller's struct up to `trim` and reads each field from there on under its
+ * own flag (trim: FLTEE_OPT_TRIM; krum_f, krum_m: FLTEE_OPT_KRUM), so a caller whose struct ends
+ * at `trim`, which never sets the flag, is unaffected, and fltee_device_opts itself keeps its
+ * size. */
+typedef struct fltee_device_opts_krum {
+    fltee_device_opts base;
+    size_t krum_f;      /* the assumed number of Byzantine clients f, and ... */
+    size_t krum_m;      /* ... the number of clients kept m */
+} fltee_device_opts_krum;
 
 /* Aggregate n clients x k records (8 B each: u32 LE idx, f32 LE val),
  * client-major, into d_out[d] (overwritten, or accumulated with
@@ -554,6 +610,36 @@ void fltee_set_dense_trim(uint32_t per_mille);
  * the pipelined path, the refusals, the root running a multi-GPU eid's trimmed call.  Nothing
  * new is revealed: the launch shapes depend on (n', d) and on whether t > FLTEE_TRIM_MAX. */
 void fltee_set_dense_trim_select(int on);
+
+/* ---- robust aggregation: Multi-Krum behind the ECALL ------------------------------------------
+ * The trimmed mean looks at one coordinate at a time; a colluding minority whose updates stay
+ * inside every coordinate's range, or are so large that each coordinate's survivors come from
+ * other clients, passes it.  Multi-Krum (FLTEE_OPT_KRUM above) scores whole clients by their
+ * squared distances to their nearest neighbours and averages the m best-scored clients whole. */
+/* Steps 1 - 4 of FLTEE_OPT_KRUM alone, device-resident: d_records is n dense uploads of d
+ * parameters (records, or the layout opts' row flag names; FLTEE_OPT_DENSE is implied), opts is
+ * the base of a fltee_device_opts_krum with FLTEE_OPT_KRUM set (INVALID_PARAMETER without the
+ * flag) and gives krum_f, krum_m and, with FLTEE_OPT_CLIP, the bound (the other options are
+ * ignored).  Leaves the n scores (f64) in d_scores and the n keep words (0 / 0xFFFFFFFF) in
+ * d_keep, device memory both; asynchronous on `stream`.  The refusals and the scratch are those
+ * of the aggregate call on alg 3.  For tests, and for hosts that drive one process per GPU. */
+fltee_status_t fltee_krum_select_device(const void *d_records, size_t n, size_t d,
+                                        const fltee_device_opts *opts, double *d_scores,
+                                        uint32_t *d_keep, void *stream);
+/* Process-wide, like fltee_set_dense_trim; (0, 0) is off and the default: every call is then
+ * launch for launch what it was.  On: an ecall_secure_aggregation call on the dense path of algs
+ * 3, 4, 5 (a dense upload in position, records or value rows; the staged and the pipelined path
+ * alike) is aggregated with FLTEE_OPT_KRUM, krum_f = f, krum_m = m, on the n' clients actually
+ * aggregated (the survivors under FLTEE_AEAD_DROP: the gather, the selection and the divisor m
+ * agree on n'); the DP noise is divided by m.  A host that switched Multi-Krum on never gets a
+ * plain mean back: what cannot be answered ends with 0x2, with the existing 0x2 refusals ([out]
+ * zero-filled, the timers written, the round kept) — algs 1, 2, 6 and 7, a sparse upload, alg 5
+ * under fltee_set_path_oram_tree(1), n' < 2 f + 3, m = 0, m > n' - f, n > FLTEE_KRUM_MAX_N,
+ * fltee_set_dense_trim on at the same time, and a dense-sized records upload out of position.
+ * On an eid over several GPUs the dense group path declines such a call and the root runs it:
+ * the one-GPU bits.  Nothing new is revealed: the launch shapes depend on (n', d) and the
+ * buffers' alignment; the keep set is never read back. */
+void fltee_set_dense_krum(uint32_t f, uint32_t m);
 
 /* ---- authenticated uploads: AES-128-GCM (NIST SP 800-38D), 96-bit IV, 128-bit tag ------
  * Per client: K = the session key, H = E_K(0^128), J0 = IV || 0x00000001, keystream block
