@@ -204,6 +204,28 @@ hipError_t launch_krum_select(const void *in, bool packed, size_t n, size_t d, s
                               const float *client_coef, void *scratch, uint32_t *status, hipStream_t s);
 hipError_t launch_krum_accumulate(const void *in, bool packed, size_t n, size_t d, const uint32_t *keep, float coef,
                                   float *out, const float *client_coef, bool accumulate, hipStream_t s);
+// gram: step 1 and the reduce alone — G (NP x NP f64) at krum_gram(scratch, geometry), behind the
+// chunks' partials; the part of the selection the geometric median shares
+double *krum_gram(void *scratch, const KrumGeom &g);
+hipError_t launch_krum_gram(const void *in, bool packed, size_t n, size_t d, const float *client_coef, void *scratch,
+                            uint32_t *status, hipStream_t s);
+
+// k_gmed.hip: the geometric median (smoothed Weiszfeld, FLTEE_OPT_GMED) of n dense uploads,
+// n <= FLTEE_KRUM_MAX_N, iterated on Krum's Gram matrix.  scratch_bytes: Krum's partials and G,
+// then NP-sized w, u, rho (f64), alpha (f32) and valid (u32) — a function of (n, d) alone.
+// weights: steps 1 - 5 (Gram, valid, iters Weiszfeld iterations with the floor nu, alpha) into
+// the scratch, where gmed_alpha / gmed_rho / gmed_valid find their n entries; status: records
+// only.  accumulate: out[j] = the in-order f32 sum of valid_c ? x_c[j] * alpha_c : +0.0 (or
+// out += that sum).
+size_t gmed_scratch_bytes(size_t n, size_t d);
+float *gmed_alpha(void *scratch, size_t n, size_t d);
+double *gmed_rho(void *scratch, size_t n, size_t d);
+uint32_t *gmed_valid(void *scratch, size_t n, size_t d);
+hipError_t launch_gmed_weights(const void *in, bool packed, size_t n, size_t d, size_t iters, double nu,
+                               const float *client_coef, void *scratch, uint32_t *status, hipStream_t s);
+hipError_t launch_gmed_accumulate(const void *in, bool packed, size_t n, size_t d, const float *alpha,
+                                  const uint32_t *valid, float *out, const float *client_coef, bool accumulate,
+                                  hipStream_t s);
 
 // k_bitonic.hip
 // valid: positions >= valid hold identical pad records (0: unknown); the stage blocks

@@ -150,6 +150,11 @@ static bool g_dense_trim_select = false;
 // every ECALL on the dense path; (0, 0) (default): off
 static uint32_t g_dense_krum_f = 0, g_dense_krum_m = 0;
 static bool dense_krum_on() { return (g_dense_krum_f | g_dense_krum_m) != 0; }
+// the geometric median (fltee_set_dense_gmed): the Weiszfeld iterations R and the smoothing floor nu
+// of every ECALL on the dense path; R = 0 (default): off
+static uint32_t g_dense_gmed_iters = 0;
+static double g_dense_gmed_nu = 0.0;
+static bool dense_gmed_on() { return g_dense_gmed_iters != 0; }
 
 // The trim count (include/fltee_agg.h fltee_trim_count): the one place it is decided.
 static size_t trim_count(size_t n, uint32_t per_mille) {
@@ -400,6 +405,8 @@ static EngineOpts ecall_opts(uint32_t alg, size_t n, size_t rpc, size_t d, size_
     // (fltee_set_dense_krum: every call carries the flag, and the plan refuses what is not a dense
     // call of a flat alg with n >= 2 f + 3, m <= n - f — never a plain mean)
     if (dense_krum_on()) o.flags |= FLTEE_OPT_KRUM, o.krum_f = g_dense_krum_f, o.krum_m = g_dense_krum_m;
+    // (fltee_set_dense_gmed likewise: the plan refuses what is not a dense call of a flat alg)
+    if (dense_gmed_on()) o.flags |= FLTEE_OPT_GMED, o.gmed_iters = g_dense_gmed_iters, o.gmed_nu = g_dense_gmed_nu;
     if (ecall_takes_tree(alg, n, rpc, d)) o.flags |= FLTEE_OPT_ORAM_TREE;
     if (alg == FLTEE_ALG_NIPS19) o.seed = seed ? seed : next_seed();
     // advanced's fold (advanced.rs:66-101) runs once with halo = n: bit for bit for every
@@ -455,8 +462,8 @@ static uint32_t aggregate_records(DeviceCtx *c, uint32_t alg, size_t n, size_t r
         bool retry = false;
         st = status_to_retval(dev_st, alg, &retry);
         if (!retry) return st;
-        // (under fltee_set_dense_trim / _krum a sparse rerun would be a plain mean: refused)
-        if (g_dense_trim || dense_krum_on()) return FLTEE_ERROR_INVALID_PARAMETER;
+        // (under fltee_set_dense_trim / _krum / _gmed a sparse rerun would be a plain mean: refused)
+        if (g_dense_trim || dense_krum_on() || dense_gmed_on()) return FLTEE_ERROR_INVALID_PARAMETER;
         o.flags &= ~FLTEE_OPT_DENSE;  // the sparse path: exact for any upload
     }
     return FLTEE_ERROR_INVALID_PARAMETER;
@@ -592,8 +599,8 @@ static uint32_t staged_ecall(DeviceCtx *c, uint32_t alg, const uint32_t *ids, si
         st = status_to_retval(*(const volatile uint32_t *)((const uint8_t *)c->pin_out.ptr + d4), alg,
                               &retry);
         if (!retry) break;
-        // (under fltee_set_dense_trim / _krum a sparse rerun would be a plain mean: refused)
-        if (g_dense_trim || dense_krum_on()) return FLTEE_ERROR_INVALID_PARAMETER;
+        // (under fltee_set_dense_trim / _krum / _gmed a sparse rerun would be a plain mean: refused)
+        if (g_dense_trim || dense_krum_on() || dense_gmed_on()) return FLTEE_ERROR_INVALID_PARAMETER;
         o.flags &= ~FLTEE_OPT_DENSE;  // the sparse path: exact for any upload
     }
     if (st) return st;
@@ -809,6 +816,13 @@ extern "C" fltee_status_t ecall_secure_aggregation(
                     trim_pm || n > FLTEE_KRUM_MAX_N || n < 2 * (size_t)g_dense_krum_f + 3 || g_dense_krum_m == 0 ||
                     g_dense_krum_m > n - g_dense_krum_f))
         return fail(FLTEE_ERROR_INVALID_PARAMETER);
+    // the geometric median (fltee_set_dense_gmed): likewise, and never together with the trim or
+    // Multi-Krum
+    const bool gmed_on = dense_gmed_on();
+    if (gmed_on && (!flat || !(fmt || rpc == d) || (aggregation_alg == FLTEE_ALG_PATH_ORAM && oram_tree_default()) ||
+                    trim_pm || krum_on || n > FLTEE_KRUM_MAX_N || g_dense_gmed_iters > FLTEE_GMED_MAX_ITERS ||
+                    !(g_dense_gmed_nu > 0.0) || !(g_dense_gmed_nu < __builtin_inf())))
+        return fail(FLTEE_ERROR_INVALID_PARAMETER);
 
     if (!c->outbuf.reserve(d * 4 + 16)) return fail(FLTEE_ERROR_OUT_OF_MEMORY);
     float *d_out = (float *)c->outbuf.ptr;
@@ -840,7 +854,8 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     // a trimmed call too — it needs every client's value of a column in one place, which a
     // column shard has, but the group's per-rank sums are untrimmed: the root runs it)
     // (a Multi-Krum call likewise: the selection needs whole clients)
-    if (G && flat && !tree && !fmt && !trim_pm && !krum_on && rpc == d && bpc == d * 8 + tagb) {
+    // (a geometric-median call too: its weights need whole clients)
+    if (G && flat && !tree && !fmt && !trim_pm && !krum_on && !gmed_on && rpc == d && bpc == d * 8 + tagb) {
         // dense uploads over a multi-GPU eid: every GPU loads and decrypts its own
         // parameter range (group.hip); "Loading" = the parallel H2D, "Decryption" = the
         // decrypt + aggregate + gather.  Authenticated: every GPU also hashes its range, the
@@ -954,7 +969,7 @@ extern "C" fltee_status_t ecall_secure_aggregation(
                                    trim_count(n_agg, trim_pm));
     }
     if (!st && cfg.dp) {  // lib.rs:399-408 (a trimmed call: the n' - 2 t clients it averaged)
-        // (a Multi-Krum call: the m clients it averaged)
+        // (a Multi-Krum call: the m clients it averaged; a geometric-median call: the n' it weighted)
         if (launch_dp_noise(d_out, d, cfg.sigma, cfg.clipping,
                             krum_on ? g_dense_krum_m : n_agg - 2 * trim_count(n_agg, trim_pm), next_seed(),
                             c->stream) != hipSuccess)
@@ -1004,9 +1019,9 @@ extern "C" fltee_status_t ecall_client_size_optimized_secure_aggregation(
     if (uint32_t st = check_uploaded(cfg, client_ids, n)) return fail(st);
     for (size_t i = 0; i < n; ++i)
         if (!g_keys.count(client_ids[i])) return fail(FLTEE_ERROR_UNEXPECTED);
-    // (fltee_set_dense_trim / _krum: alg 6 is sort-based and cannot be trimmed or scored — never a
-    // plain mean)
-    if (g_dense_trim || dense_krum_on()) return fail(FLTEE_ERROR_INVALID_PARAMETER);
+    // (fltee_set_dense_trim / _krum / _gmed: alg 6 is sort-based and cannot be trimmed, scored or
+    // weighted — never a plain mean)
+    if (g_dense_trim || dense_krum_on() || dense_gmed_on()) return fail(FLTEE_ERROR_INVALID_PARAMETER);
 
     const bool aead = g_upload_aead;
     if (aead && !gcm_sizes_ok(k * 8, 16)) return fail(FLTEE_ERROR_INVALID_PARAMETER);
@@ -1336,6 +1351,11 @@ extern "C" size_t fltee_trim_count(size_t n, uint32_t per_mille) { return trim_c
 extern "C" void fltee_set_dense_trim_select(int on) {
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
     g_dense_trim_select = on != 0;
+}
+
+extern "C" void fltee_set_dense_gmed(uint32_t iters, double nu) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    g_dense_gmed_iters = iters, g_dense_gmed_nu = nu;
 }
 
 extern "C" void fltee_set_dense_krum(uint32_t f, uint32_t m) {

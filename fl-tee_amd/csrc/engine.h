@@ -54,6 +54,8 @@ enum Route : uint32_t {
     kRouteFp8,           // flat algs, FLTEE_OPT_FP8: the fp8 accumulate (k_rows.hip)
     kRouteKrumDense,     // flat algs, FLTEE_OPT_KRUM on records: Multi-Krum (k_krum.hip; its scratch in ws_mat)
     kRouteKrumPacked,    // ... on packed rows
+    kRouteGmedDense,     // flat algs, FLTEE_OPT_GMED on records: the geometric median (k_gmed.hip; its scratch in ws_mat)
+    kRouteGmedPacked,    // ... on packed rows
 };
 enum Tail : uint32_t {
     kTailNone,
@@ -74,9 +76,12 @@ struct AdvShape {
 };
 
 // A call's options as the engine holds them: the public struct, and behind it the fields of
-// fltee_device_opts_krum (read_opts fills them under FLTEE_OPT_KRUM; zero otherwise).
+// fltee_device_opts_krum (read_opts fills them under FLTEE_OPT_KRUM; zero otherwise) and of
+// fltee_device_opts_gmed (under FLTEE_OPT_GMED).
 struct EngineOpts : fltee_device_opts {
     size_t krum_f, krum_m;
+    size_t gmed_iters;
+    double gmed_nu;
 };
 
 // The one decision about a call's public shape (alg, n, k, d, opts): whether it is refused,
@@ -163,6 +168,10 @@ fltee_status_t aggregate(uint32_t alg, const void *rec, size_t n, size_t k, size
 // sel_keep (device memory), nothing written to an output
 fltee_status_t krum_select(const void *rec, size_t n, size_t d, const EngineOpts &o, double *sel_scores,
                            uint32_t *sel_keep, hipStream_t s, uint32_t *status);
+// a FLTEE_OPT_GMED call up to its weights: the n alpha and the last iteration's n rho copied to
+// sel_alpha / sel_rho (device memory), nothing written to an output
+fltee_status_t gmed_weights(const void *rec, size_t n, size_t d, const EngineOpts &o, float *sel_alpha,
+                            double *sel_rho, hipStream_t s, uint32_t *status);
 // common.rs:25-35 on m entries of src (the shuffled array), bit-exact: out[i] = coef *
 // (+0 + v1 + v2 ...) over the entries with idx == i in position order (accumulate:
 // out[i] += the un-scaled sum).  Synchronises `s` once to read the selected count.

@@ -282,6 +282,17 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpt
                   n > FLTEE_KRUM_MAX_N || o.krum_f > n || n < 2 * o.krum_f + 3 ||  // (f > n: 2 f may wrap)
                   o.krum_m == 0 || o.krum_m > n - o.krum_f);
     }
+    // the geometric median (FLTEE_OPT_GMED, k_gmed.hip): a dense call on the flat algs without the
+    // tree, n <= FLTEE_KRUM_MAX_N, 1 <= R <= FLTEE_GMED_MAX_ITERS, nu finite and above 0; never
+    // together with the trim, Multi-Krum or NO_AVERAGE (a weighted mean has no partial-sum form)
+    const bool gmed = (o.flags & FLTEE_OPT_GMED) != 0;
+    if (gmed) {
+        const bool flat = alg == FLTEE_ALG_BASELINE || alg == FLTEE_ALG_NON_OBLIVIOUS || alg == FLTEE_ALG_PATH_ORAM;
+        refuse_if(!flat || !dense || trim || krum || (o.flags & FLTEE_OPT_NO_AVERAGE) ||
+                  (o.flags & (FLTEE_OPT_ORAM_TREE | FLTEE_OPT_ORAM_LAZY)) || n > FLTEE_KRUM_MAX_N ||
+                  o.gmed_iters == 0 || o.gmed_iters > FLTEE_GMED_MAX_ITERS ||
+                  !(o.gmed_nu > 0.0) || !(o.gmed_nu < __builtin_inf()));  // (a NaN fails both compares)
+    }
     switch (alg) {
     case FLTEE_ALG_PATH_ORAM:
     case FLTEE_ALG_BASELINE:
@@ -310,6 +321,11 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpt
                 p.route = packed ? kRouteKrumPacked : kRouteKrumDense;
                 // the Gram partials, G, the scores and the keep words: a slot no dense route touches
                 p.bytes[kWsMat] = n <= FLTEE_KRUM_MAX_N ? krum_scratch_bytes(n, d) : 0;
+            }
+            if (gmed) {
+                p.route = packed ? kRouteGmedPacked : kRouteGmedDense;
+                // Krum's partials and G, then w, u, rho, alpha and valid: from (n, d) alone
+                p.bytes[kWsMat] = n && n <= FLTEE_KRUM_MAX_N ? gmed_scratch_bytes(n, d) : 0;  // (refused otherwise)
             }
         } else if (alg == FLTEE_ALG_NON_OBLIVIOUS && use_scatter_rows(n, k, d)) {
             p.route = kRouteScatterRows;
@@ -373,13 +389,15 @@ static Plan plan_for(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpt
         p.clip_records = p.route != kRouteDense && p.route != kRoutePacked && p.route != kRouteTrimDense &&
                          p.route != kRouteTrimPacked && p.route != kRouteBf16 && p.route != kRouteFp8 &&
                          p.route != kRouteTrimSelectDense && p.route != kRouteTrimSelectPacked &&
-                         p.route != kRouteKrumDense && p.route != kRouteKrumPacked;
+                         p.route != kRouteKrumDense && p.route != kRouteKrumPacked &&
+                         p.route != kRouteGmedDense && p.route != kRouteGmedPacked;
         if (p.clip_records) p.bytes[kWsRec] = nrec * 8;
     }
     // every route but the packed / bf16 / fp8 accumulate reads records: the plan (n, d, d) has, on the
     // rows unpacked into the record scratch (where FLTEE_OPT_CLIP then clips them in place)
     p.unpack = fmt != kRowsNone && p.route != kRoutePacked && p.route != kRouteTrimPacked && p.route != kRouteBf16 &&
-               p.route != kRouteTrimSelectPacked && p.route != kRouteFp8 && p.route != kRouteKrumPacked;
+               p.route != kRouteTrimSelectPacked && p.route != kRouteFp8 && p.route != kRouteKrumPacked &&
+               p.route != kRouteGmedPacked;
     if (p.unpack) p.bytes[kWsRec] = nrec * 8;
     return p;
 }
@@ -593,10 +611,12 @@ hipError_t advanced_batch(const void *rec, size_t n, size_t k, size_t d, size_t 
 
 // plan -> the refusal -> the plan's scratch -> clip -> the route -> DP
 // sel_scores / sel_keep (krum_select): a Multi-Krum call ends after its selection, the scores and
-// keep words copied there
+// keep words copied there; sel_alpha / sel_rho (gmed_weights): a geometric-median call after its
+// weights likewise
 static fltee_status_t aggregate_impl(uint32_t alg, const void *rec, size_t n, size_t k, size_t d, float *out,
                                      const EngineOpts &o, hipStream_t s, uint32_t *status,
-                                     double *sel_scores, uint32_t *sel_keep) {
+                                     double *sel_scores, uint32_t *sel_keep, float *sel_alpha = nullptr,
+                                     double *sel_rho = nullptr) {
     DeviceCtx *c = current_ctx();
     if (!c) return FLTEE_ERROR_UNEXPECTED;
     const Plan p = plan_for(alg, n, k, d, o);
@@ -686,6 +706,22 @@ static fltee_status_t aggregate_impl(uint32_t alg, const void *rec, size_t n, si
             e = launch_krum_accumulate(rec, rows, n, d, krum_keep(c->ws_mat.ptr, n, d), coef, out, ccoef, acc, s);
         break;
     }
+    case kRouteGmedDense:
+    case kRouteGmedPacked: {
+        const bool rows = p.route == kRouteGmedPacked;
+        void *ws = c->ws_mat.ptr;
+        c->mat_clean = 0;  // (the scatter rows' sentinel, if it was there, is overwritten)
+        e = launch_gmed_weights(rec, rows, n, d, o.gmed_iters, o.gmed_nu, ccoef, ws, status, s);
+        if (e == hipSuccess && sel_alpha) {
+            e = fl_memcpy_async(sel_alpha, gmed_alpha(ws, n, d), n * 4, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = fl_memcpy_async(sel_rho, gmed_rho(ws, n, d), n * 8, hipMemcpyDeviceToDevice, s);
+            return e == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+        }
+        // (the weights sum to one: no averaging factor; n_avg is the DP noise's divisor alone)
+        if (e == hipSuccess)
+            e = launch_gmed_accumulate(rec, rows, n, d, gmed_alpha(ws, n, d), gmed_valid(ws, n, d), out, ccoef, acc, s);
+        break;
+    }
     case kRouteScatterRows:
         if (c->mat_clean_ptr != c->ws_mat.ptr || c->mat_clean_cap != c->ws_mat.cap) {
             c->mat_clean = 0;  // a new allocation: contents unknown
@@ -772,6 +808,13 @@ fltee_status_t krum_select(const void *rec, size_t n, size_t d, const EngineOpts
     return aggregate_impl(FLTEE_ALG_BASELINE, rec, n, d, d, nullptr, o, s, status, sel_scores, sel_keep);
 }
 
+fltee_status_t gmed_weights(const void *rec, size_t n, size_t d, const EngineOpts &o, float *sel_alpha,
+                            double *sel_rho, hipStream_t s, uint32_t *status) {
+    if (!(o.flags & FLTEE_OPT_GMED) || !sel_alpha || !sel_rho) return FLTEE_ERROR_INVALID_PARAMETER;
+    return aggregate_impl(FLTEE_ALG_BASELINE, rec, n, d, d, nullptr, o, s, status, nullptr, nullptr, sel_alpha,
+                          sel_rho);
+}
+
 size_t workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d, const EngineOpts &o) {
     const Plan p = plan_for(alg, n, k, d, o);
     size_t sum = 0;
@@ -823,7 +866,8 @@ static EngineOpts default_opts() {
 
 // The caller's options.  The struct is copied up to `trim`; each field from there on is read
 // only under its own flag (trim: FLTEE_OPT_TRIM; krum_f, krum_m, which lie behind the struct in a
-// fltee_device_opts_krum: FLTEE_OPT_KRUM): a caller built against a struct that ended earlier
+// fltee_device_opts_krum: FLTEE_OPT_KRUM; gmed_iters, gmed_nu, behind it in a
+// fltee_device_opts_gmed: FLTEE_OPT_GMED): a caller built against a struct that ended earlier
 // never sets the flag, and nothing past its struct is touched.
 static EngineOpts read_opts(const fltee_device_opts *opts) {
     EngineOpts o = default_opts();
@@ -833,6 +877,10 @@ static EngineOpts read_opts(const fltee_device_opts *opts) {
     if (o.flags & FLTEE_OPT_KRUM) {
         const fltee_device_opts_krum *k = reinterpret_cast<const fltee_device_opts_krum *>(opts);
         o.krum_f = k->krum_f, o.krum_m = k->krum_m;
+    }
+    if (o.flags & FLTEE_OPT_GMED) {
+        const fltee_device_opts_gmed *g = reinterpret_cast<const fltee_device_opts_gmed *>(opts);
+        o.gmed_iters = g->gmed_iters, o.gmed_nu = g->gmed_nu;
     }
     return o;
 }
@@ -878,6 +926,30 @@ extern "C" fltee_status_t fltee_krum_select_device(const void *d_records, size_t
     return krum_select(d_records, n, d, o, d_scores, d_keep, s, status);
 }
 
+extern "C" fltee_status_t fltee_gmed_weights_device(const void *d_records, size_t n, size_t d,
+                                                    const fltee_device_opts *opts, float *d_alpha,
+                                                    double *d_rho, void *stream) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    // (the flag is the caller's word that opts is the base of a fltee_device_opts_gmed)
+    if (!opts || !(opts->flags & FLTEE_OPT_GMED) || !d_alpha || !d_rho) return FLTEE_ERROR_INVALID_PARAMETER;
+    // steps 1 - 5 take the layout, the clip and (R, nu) from the options and nothing else
+    const EngineOpts in = read_opts(opts);
+    EngineOpts o = default_opts();
+    o.flags = (in.flags & (FLTEE_OPT_PACKED | FLTEE_OPT_BF16 | FLTEE_OPT_FP8 | FLTEE_OPT_CLIP)) | FLTEE_OPT_DENSE |
+              FLTEE_OPT_GMED;
+    o.clipping = in.clipping, o.d_status = in.d_status;
+    o.gmed_iters = in.gmed_iters, o.gmed_nu = in.gmed_nu;
+    if ((o.flags & FLTEE_OPT_BF16) && ((uintptr_t)d_records & 1)) return FLTEE_ERROR_INVALID_PARAMETER;
+    if ((o.flags & FLTEE_OPT_FP8) && ((uintptr_t)d_records & 3)) return FLTEE_ERROR_INVALID_PARAMETER;
+    if (plan_status(FLTEE_ALG_BASELINE, n, d, d, o) != FLTEE_SUCCESS) return FLTEE_ERROR_INVALID_PARAMETER;
+    DeviceCtx *c = current_ctx();
+    if (!c) return FLTEE_ERROR_UNEXPECTED;
+    uint32_t *status = o.d_status ? o.d_status : c->status;
+    hipStream_t s = (hipStream_t)stream;
+    if (!o.d_status && fl_memset_async(c->status, 0, 4, s) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+    return gmed_weights(d_records, n, d, o, d_alpha, d_rho, s, status);
+}
+
 extern "C" size_t fltee_workspace_bytes(uint32_t alg, size_t n, size_t k, size_t d,
                                         const fltee_device_opts *opts) {
     const EngineOpts o = read_opts(opts);
@@ -889,7 +961,7 @@ extern "C" fltee_status_t fltee_reserve(uint32_t alg, size_t n, size_t k, size_t
     std::lock_guard<std::recursive_mutex> lk(api_mutex());
     const EngineOpts o = read_opts(opts);
     // a refused trimmed call is refused here too, by the plan, before anything is reserved
-    if ((o.flags & (FLTEE_OPT_TRIM | FLTEE_OPT_TRIM_SELECT | FLTEE_OPT_KRUM)) &&
+    if ((o.flags & (FLTEE_OPT_TRIM | FLTEE_OPT_TRIM_SELECT | FLTEE_OPT_KRUM | FLTEE_OPT_GMED)) &&
         plan_status(alg, n, k, d, o) != FLTEE_SUCCESS)
         return FLTEE_ERROR_INVALID_PARAMETER;
     return reserve(alg, n, k, d, o) ? FLTEE_SUCCESS : FLTEE_ERROR_OUT_OF_MEMORY;

@@ -72,7 +72,7 @@ size_t krum_scratch_bytes(size_t n, size_t d) {
     return (g.chunks + 1) * g.np * g.np * 8 + g.np * 8 + g.np * 4;
 }
 static double *krum_part(void *ws) { return (double *)ws; }
-static double *krum_gram(void *ws, const KrumGeom &g) { return (double *)ws + g.chunks * g.np * g.np; }
+double *krum_gram(void *ws, const KrumGeom &g) { return (double *)ws + g.chunks * g.np * g.np; }
 double *krum_scores(void *ws, size_t n, size_t d) {
     const KrumGeom g = krum_geometry(n, d);
     return krum_gram(ws, g) + g.np * g.np;
@@ -343,14 +343,13 @@ static void launch_gram(const void *in, size_t stride, size_t n, size_t d, const
                      ccoef, part, status);
 }
 
-hipError_t launch_krum_select(const void *in, bool packed, size_t n, size_t d, size_t f, size_t m,
-                              const float *client_coef, void *scratch, uint32_t *status, hipStream_t s) {
-    // (the plan refuses these)
-    if (n > FLTEE_KRUM_MAX_N || n < 2 * f + 3 || m == 0 || m > n - f || d >= ((size_t)1 << 31))
-        return hipErrorInvalidValue;
+// steps 1 and the reduce: G (NP x NP f64, krum_geometry(n, d)'s NP) from the chunks' partials; the
+// scratch's first (chunks + 1) NP^2 doubles.  Shared with the geometric median (k_gmed.hip).
+hipError_t launch_krum_gram(const void *in, bool packed, size_t n, size_t d, const float *client_coef, void *scratch,
+                            uint32_t *status, hipStream_t s) {
+    if (n == 0 || n > FLTEE_KRUM_MAX_N || d >= ((size_t)1 << 31)) return hipErrorInvalidValue;
     const KrumGeom g = krum_geometry(n, d);
-    double *part = krum_part(scratch), *G = krum_gram(scratch, g), *scores = krum_scores(scratch, n, d);
-    uint32_t *keep = krum_keep(scratch, n, d);
+    double *part = krum_part(scratch), *G = krum_gram(scratch, g);
     const uintptr_t a = (uintptr_t)in;
     if (packed) {
         const size_t stride = RowF32::row_stride(d);  // floats
@@ -363,6 +362,18 @@ hipError_t launch_krum_select(const void *in, bool packed, size_t n, size_t d, s
     }
     FLTEE_LAUNCH(krum_reduce_kernel, dim3((unsigned)((g.np * g.np + 255) / 256)), dim3(256), 0, s, part,
                  (uint32_t)g.np, (uint32_t)g.chunks, G);
+    return hipGetLastError();
+}
+
+hipError_t launch_krum_select(const void *in, bool packed, size_t n, size_t d, size_t f, size_t m,
+                              const float *client_coef, void *scratch, uint32_t *status, hipStream_t s) {
+    // (the plan refuses these)
+    if (n > FLTEE_KRUM_MAX_N || n < 2 * f + 3 || m == 0 || m > n - f || d >= ((size_t)1 << 31))
+        return hipErrorInvalidValue;
+    const KrumGeom g = krum_geometry(n, d);
+    double *G = krum_gram(scratch, g), *scores = krum_scores(scratch, n, d);
+    uint32_t *keep = krum_keep(scratch, n, d);
+    if (hipError_t e = launch_krum_gram(in, packed, n, d, client_coef, scratch, status, s)) return e;
     size_t P = 64;
     while (P < n) P <<= 1;
     FLTEE_LAUNCH(krum_score_kernel, dim3((unsigned)n), dim3((unsigned)P), 0, s, G, (uint32_t)g.np, (uint32_t)n,

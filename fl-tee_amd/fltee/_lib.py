@@ -58,6 +58,8 @@ OPT_TRIM_SELECT = 0x800  # with OPT_TRIM: trim by selection (k_trim_select.hip),
 TRIM_SELECT_MAX_N = 4096  # FLTEE_TRIM_SELECT_MAX_N
 OPT_KRUM = 0x2000  # Multi-Krum of a dense call (k_krum.hip): DeviceOptsKrum.krum_f assumed Byzantine, krum_m kept
 KRUM_MAX_N = 1024  # FLTEE_KRUM_MAX_N
+OPT_GMED = 0x4000  # the geometric median of a dense call (k_gmed.hip): DeviceOptsGmed.gmed_iters Weiszfeld iterations, floor gmed_nu
+GMED_MAX_ITERS = 64  # FLTEE_GMED_MAX_ITERS
 
 
 class DeviceOpts(ctypes.Structure):
@@ -82,6 +84,16 @@ class DeviceOptsKrum(DeviceOpts):
     _fields_ = [
         ("krum_f", ctypes.c_size_t),
         ("krum_m", ctypes.c_size_t),
+    ]
+
+
+class DeviceOptsGmed(DeviceOpts):
+    """struct fltee_device_opts_gmed: the options of an OPT_GMED call, DeviceOpts with the iteration
+    count and the smoothing floor behind it (passed wherever a DeviceOpts pointer is taken; read
+    under the flag)."""
+    _fields_ = [
+        ("gmed_iters", ctypes.c_size_t),
+        ("gmed_nu", ctypes.c_double),
     ]
 
 
@@ -119,6 +131,8 @@ SIGNATURES = {
     "fltee_set_dense_trim_select": (None, [ctypes.c_int]),
     "fltee_krum_select_device": (_U32, [_P, _S, _S, ctypes.POINTER(DeviceOpts), _P, _P, _P]),
     "fltee_set_dense_krum": (None, [_U32, _U32]),
+    "fltee_gmed_weights_device": (_U32, [_P, _S, _S, ctypes.POINTER(DeviceOpts), _P, _P, _P]),
+    "fltee_set_dense_gmed": (None, [_U32, ctypes.c_double]),
     "fltee_bf16_slice_bytes": (_S, [_S]),
     "fltee_upload_is_bf16": (ctypes.c_int, [ctypes.c_int, _S, _S, _S]),
     "fltee_set_upload_bf16": (None, [ctypes.c_int]),

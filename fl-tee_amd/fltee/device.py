@@ -39,8 +39,10 @@ def unpack_records(rec):
 def opts(*, dense=False, dp=False, clip=False, accumulate=False, no_average=False, sigma=1.12,
          clipping=1.0, seed=0, k_req=None, batch=0, n_avg=0, fold_halo=0, status=None,
          oram_tree=False, oram_lazy=False, packed=False, trim=None, bf16=False, trim_select=False,
-         fp8=False, krum=None):
-    o = L.DeviceOptsKrum() if krum is not None else L.DeviceOpts()
+         fp8=False, krum=None, gmed=None):
+    if krum is not None and gmed is not None:  # (two structs, one pointer; the plan refuses the pair anyway)
+        raise ValueError("krum= and gmed= are alternatives")
+    o = L.DeviceOptsKrum() if krum is not None else L.DeviceOptsGmed() if gmed is not None else L.DeviceOpts()
     o.flags = ((L.OPT_DENSE if dense else 0) | (L.OPT_DP if dp else 0) | (L.OPT_CLIP if clip else 0)
                | (L.OPT_ACCUMULATE if accumulate else 0) | (L.OPT_NO_AVERAGE if no_average else 0)
                | (L.OPT_ORAM_TREE if oram_tree else 0) | (L.OPT_ORAM_LAZY if oram_lazy else 0)
@@ -58,6 +60,9 @@ def opts(*, dense=False, dp=False, clip=False, accumulate=False, no_average=Fals
     if krum is not None:  # Multi-Krum of a dense call: (f assumed Byzantine clients, m clients kept)
         o.flags |= L.OPT_KRUM
         o.krum_f, o.krum_m = krum
+    if gmed is not None:  # the geometric median of a dense call: (Weiszfeld iterations R, smoothing floor nu)
+        o.flags |= L.OPT_GMED
+        o.gmed_iters, o.gmed_nu = gmed
     o.d_status = status.data_ptr() if status is not None else None
     return o
 
@@ -74,7 +79,9 @@ def aggregate(alg, records, n, k, d, out=None, stream=None, **kw):
     bf16=True: n bf16 slices (n * bf16_row(d) halves' worth of bytes, 2-byte aligned).
     fp8=True: n fp8 slices (n * fp8_row(d) bytes, 4-byte aligned).
     krum=(f, m): Multi-Krum of a dense call on algs 3, 4, 5 — the m clients with the smallest sums
-    of squared distances to their n - f - 2 nearest neighbours, averaged whole."""
+    of squared distances to their n - f - 2 nearest neighbours, averaged whole.
+    gmed=(R, nu): the geometric median of a dense call on algs 3, 4, 5 — R smoothed Weiszfeld
+    iterations with the floor nu, every valid client kept with a weight 1 / max(nu, distance)."""
     if kw.get("fp8"):
         assert records.is_cuda and records.numel() * records.element_size() >= n * fp8_row(d)
     elif kw.get("bf16"):
@@ -103,6 +110,19 @@ def krum_select(records, n, d, f, m, stream=None, **kw):
     _check(L.lib().fltee_krum_select_device(_ptr(records), n, d, ctypes.byref(o), _ptr(scores), _ptr(keep),
                                             _stream(stream)), "fltee_krum_select_device")
     return scores, keep
+
+
+def gmed_weights(records, n, d, iters, nu, stream=None, **kw):
+    """fltee_gmed_weights_device: the geometric median's weights alone, on n dense uploads of d
+    parameters (records, or packed= / bf16= / fp8= rows; clip= with clipping=) ->
+    (alpha float32 [n], rho float64 [n]: the last iteration's distances), cuda tensors."""
+    assert records.is_cuda
+    o = opts(gmed=(iters, nu), **kw)
+    alpha = torch.empty(n, dtype=torch.float32, device=records.device)
+    rho = torch.empty(n, dtype=torch.float64, device=records.device)
+    _check(L.lib().fltee_gmed_weights_device(_ptr(records), n, d, ctypes.byref(o), _ptr(alpha), _ptr(rho),
+                                             _stream(stream)), "fltee_gmed_weights_device")
+    return alpha, rho
 
 
 def packed_row(d):

@@ -112,6 +112,10 @@ class Enclave:
         """fltee_set_dense_krum (process-wide; see the module function of the same name)."""
         set_dense_krum(f, m)
 
+    def set_dense_gmed(self, iters, nu=2.0 ** -20):
+        """fltee_set_dense_gmed (process-wide; see the module function of the same name)."""
+        set_dense_gmed(iters, nu)
+
     def set_dense_trim_select(self, on):
         """fltee_set_dense_trim_select (process-wide; see the module function of the same name)."""
         set_dense_trim_select(on)
@@ -197,6 +201,20 @@ def set_dense_krum(f, m):
     if f < 0 or m < 0 or f >= 2 ** 32 or m >= 2 ** 32:
         raise ValueError(f"krum (f, m) = ({f}, {m}) is not a pair of u32")
     L.lib().fltee_set_dense_krum(f, m)
+
+
+def set_dense_gmed(iters, nu=2.0 ** -20):
+    """The geometric median (fltee_set_dense_gmed; iters = 0, the default, is off): while on, a dense
+    or packed ecall_secure_aggregation call on algs 3, 4, 5 returns the smoothed Weiszfeld iterate
+    after `iters` iterations — every valid client weighted by 1 / max(nu, its distance to the
+    iterate), the weights normalised to one.  Every call that cannot be answered so (algs 1, 2, 6,
+    7, a sparse upload, the tree, more than KRUM_MAX_N clients, more than GMED_MAX_ITERS iterations,
+    a nu that is not a finite value above 0, set_dense_trim or set_dense_krum on as well) ends with
+    retval 0x2, never with a plain mean."""
+    iters, nu = int(iters), float(nu)
+    if iters < 0 or iters >= 2 ** 32:
+        raise ValueError(f"gmed iters = {iters} is not a u32")
+    L.lib().fltee_set_dense_gmed(iters, nu)
 
 
 def trim_count(n, per_mille):

@@ -10,7 +10,7 @@ code); the handlers are fltee.server.Aggregator, the server.rs logic over the C 
                                 [--strict-reference] [--quiet]
                                 [--aead [--aead-policy abort|report|drop]]
                                 [--packed-dense] [--bf16-dense] [--fp8-dense] [--trim-per-mille N [--trim-select]]
-                                [--krum-f N --krum-m M]
+                                [--krum-f N --krum-m M] [--gmed-iters N [--gmed-nu X]]
 
 Like the reference: verbose on, dp off (server.rs:236-237; --dp turns DP on for
 the configs[3] runs), one enclave per process; calls are serialised by the
@@ -147,12 +147,23 @@ def main(argv=None):
                     help="Multi-Krum: the M best-scored clients are averaged whole (0 with --krum-f 0: "
                          "off); requests that cannot be answered so are refused, and --trim-per-mille "
                          "cannot be on at the same time")
+    ap.add_argument("--gmed-iters", type=int, default=0, metavar="N",
+                    help="the geometric median (RFA) of dense uploads (algs 3, 4, 5): N smoothed Weiszfeld "
+                         "iterations, 1 to 64 (0: off); requests that cannot be answered so are refused, and "
+                         "--trim-per-mille / --krum-f cannot be on at the same time")
+    ap.add_argument("--gmed-nu", type=float, default=2.0 ** -20, metavar="X",
+                    help="with --gmed-iters: the smoothing floor, the smallest distance that still "
+                         "lowers a client's weight (a finite value above 0; default 2^-20)")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     if (args.krum_f or args.krum_m) and args.trim_per_mille:
         ap.error("--krum-f / --krum-m and --trim-per-mille are alternatives")
     if args.krum_f < 0 or args.krum_m < 0 or (args.krum_f and not args.krum_m):
         ap.error("--krum-f needs a positive --krum-m")
+    if args.gmed_iters and (args.krum_f or args.krum_m or args.trim_per_mille):
+        ap.error("--gmed-iters, --krum-f / --krum-m and --trim-per-mille are alternatives")
+    if not 0 <= args.gmed_iters <= 64 or not 0 < args.gmed_nu < float("inf"):
+        ap.error("--gmed-iters takes 0 to 64, --gmed-nu a finite value above 0")
     if args.aead_policy is not None and not args.aead:
         ap.error("--aead-policy needs --aead")
     agg = Aggregator(device=args.device, verbose=not args.quiet, dp=args.dp,
@@ -160,7 +171,8 @@ def main(argv=None):
                      aead_policy=args.aead_policy or "abort", min_survivors=args.aead_min_survivors,
                      packed=args.packed_dense, trim_per_mille=args.trim_per_mille,
                      bf16=args.bf16_dense, trim_select=args.trim_select, fp8=args.fp8_dense,
-                     krum=(args.krum_f, args.krum_m) if (args.krum_f or args.krum_m) else None)
+                     krum=(args.krum_f, args.krum_m) if (args.krum_f or args.krum_m) else None,
+                     gmed=(args.gmed_iters, args.gmed_nu) if args.gmed_iters else None)
     server, port = make_server(agg, args.address, verbose=not args.quiet)
     server.start()
     print(f"[Server] Now GRPC Server is binded on {args.address} (port {port})", flush=True)

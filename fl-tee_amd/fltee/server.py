@@ -46,12 +46,16 @@ request).  Documented deviations from the reference host:
     m best-scored clients are averaged whole.  An alternative to `trim_per_mille` (both on: every
     request is refused); a request that cannot be answered so is a ServerPanic (retval 0x2),
     never a plain mean.
+  * `gmed=(iters, nu)` (None, off, by default) answers dense uploads to algs 3, 4, 5 with the
+    geometric median (RFA): `iters` smoothed Weiszfeld iterations with the floor `nu`, every valid
+    client kept with a smooth weight.  An alternative to `trim_per_mille` and `krum`; a request that
+    cannot be answered so is a ServerPanic (retval 0x2), never a plain mean.
 """
 import argparse
 import time
 
 from . import _lib as L
-from .ecalls import (AEAD_POLICIES, Enclave, set_dense_krum, set_dense_trim, set_dense_trim_select, set_upload_aead,
+from .ecalls import (AEAD_POLICIES, Enclave, set_dense_gmed, set_dense_krum, set_dense_trim, set_dense_trim_select, set_upload_aead,
                      set_upload_aead_policy, set_upload_bf16, set_upload_fp8, set_upload_packed)
 
 
@@ -73,7 +77,7 @@ def per_mille(text):
 class Aggregator:
     def __init__(self, device=0, verbose=False, dp=False, strict_reference=False, enclave=None,
                  aead=False, aead_policy="abort", min_survivors=1, packed=False, trim_per_mille=0,
-                 bf16=False, trim_select=False, fp8=False, krum=None):
+                 bf16=False, trim_select=False, fp8=False, krum=None, gmed=None):
         if aead_policy not in AEAD_POLICIES:
             raise ValueError(f"aead_policy must be one of {sorted(AEAD_POLICIES)}")
         if aead_policy != "abort" and not aead:
@@ -105,6 +109,9 @@ class Aggregator:
         self.krum = tuple(int(v) for v in krum) if krum is not None else None
         if self.krum is not None:  # process-wide too
             set_dense_krum(*self.krum)
+        self.gmed = (int(gmed[0]), float(gmed[1])) if gmed is not None else None
+        if self.gmed is not None:  # process-wide too
+            set_dense_gmed(*self.gmed)
         self.verbose = verbose
         self.dp = dp
         self.strict_reference = strict_reference

@@ -338,6 +338,57 @@ fltee_status_t ecall_client_size_optimized_secure_aggregation(
                                       the flag together with FLTEE_OPT_TRIM (the two robust aggregates
                                       are alternatives) */
 #define FLTEE_KRUM_MAX_N 1024
+#define FLTEE_OPT_GMED 0x4000u     /* the geometric median of a dense call (k_gmed.hip): the "RFA" of
+                                      Pillutla, Kakade and Harchaoui (2022), R iterations of the smoothed
+                                      Weiszfeld iteration.  Algs 3, 4, 5 with FLTEE_OPT_DENSE or
+                                      FLTEE_OPT_PACKED, k = d; opts is a fltee_device_opts_gmed (below):
+                                      R = gmed_iters, 1 <= R <= FLTEE_GMED_MAX_ITERS, and the smoothing
+                                      floor nu = gmed_nu, a finite f64 > 0.  A FLTEE_OPT_BF16 / _FP8 call
+                                      runs on its unpacked records, as a Krum call does.  x_c[j] is the
+                                      value the dense route would add for client c at j (FLTEE_OPT_CLIP:
+                                      v * coef_c rounded).  All f64 arithmetic is round-to-nearest add,
+                                      multiply, divide and square root, never contracted.  sum64(v), the
+                                      one reduction order, over indices 0 .. n - 1: p_l = the sum of v_i
+                                      over i = l (mod 64), ascending, from +0.0; the result is
+                                      p_0 ... p_63 added in ascending l, from +0.0.
+                                        1. G = FLTEE_OPT_KRUM's step 1: the same kernels, geometry and
+                                           summation order;
+                                        2. valid_c = G[c][c] is finite: a row of finite f32 values is
+                                           always valid, a row that holds an inf or a NaN is not;
+                                        3. w_c = valid_c ? 1.0 : 0.0;
+                                        4. R times: s = sum64(w);
+                                           u_a = sum64 over b of (valid_b ? G[a][b] * w_b : +0.0), a
+                                           select, never a product with 0;
+                                           q = sum64 over a of (valid_a ? w_a * u_a : +0.0);
+                                           inv = s > 0 ? 1 / s : 0;
+                                           D_a = (G[a][a] - 2 * (u_a * inv)) + (q * inv) * inv, not
+                                           finite -> +inf, not above 0 -> +0.0;
+                                           rho_a = sqrt(D_a); w_a = valid_a ? 1 / max(nu, rho_a) : 0;
+                                        5. s = sum64(w); alpha_c = (f32)(s > 0 ? w_c / s : 0): one f64
+                                           divide, then one rounding to f32;
+                                        6. out[j] = (((+0.0 + y_0) + y_1) + ...) in f32 in upload order,
+                                           y_c = valid_c ? x_c[j] * alpha_c rounded : +0.0.  The weights
+                                           sum to one: no averaging factor.  FLTEE_OPT_ACCUMULATE:
+                                           out += that sum.  n_avg only sets the DP noise's divisor
+                                           (n_avg ? n_avg : n).  Every client invalid: a vector of +0.0.
+                                      The limit of the Gram form: a distance is resolved only down to
+                                      about sqrt(n * 2^-52) * max |x_c|; below that D clamps to 0 and the
+                                      weight is 1 / nu.  nu is therefore the host's statement of the
+                                      smallest distance it cares about, and is taken as given.
+                                      Oblivious: every value is read at a fixed address (twice); valid
+                                      and the clamps are selects; the launch shapes depend on (n, d, R)
+                                      and the pointers' alignment.  The weights never leave the device.
+                                      Scratch: Krum's Gram partials and G, then w, u, rho, alpha and
+                                      valid, sized from (n, d) alone (R and nu move no byte); the records
+                                      layout raises FLTEE_DEV_ERR_DENSE_ORDER as the dense route does
+                                      (reported, not followed).  Refused with INVALID_PARAMETER by host
+                                      arithmetic, before anything is reserved or launched: any other
+                                      alg, a call that is not dense, FLTEE_OPT_ORAM_TREE / _LAZY, n = 0,
+                                      n > FLTEE_KRUM_MAX_N, R = 0, R > FLTEE_GMED_MAX_ITERS, a nu that is
+                                      not a finite value above 0, and the flag together with
+                                      FLTEE_OPT_TRIM, FLTEE_OPT_KRUM or FLTEE_OPT_NO_AVERAGE (a weighted
+                                      mean has no partial-sum form) */
+#define FLTEE_GMED_MAX_ITERS 64
 
 typedef struct fltee_device_opts {
     uint32_t flags;     /* FLTEE_OPT_* */
@@ -369,6 +420,14 @@ typedef struct fltee_device_opts_krum {
     size_t krum_f;      /* the assumed number of Byzantine clients f, and ... */
     size_t krum_m;      /* ... the number of clients kept m */
 } fltee_device_opts_krum;
+
+/* The options of a FLTEE_OPT_GMED call, by the same pattern: fltee_device_opts with the iteration
+ * count and the smoothing floor behind `trim`, read only under FLTEE_OPT_GMED. */
+typedef struct fltee_device_opts_gmed {
+    fltee_device_opts base;
+    size_t gmed_iters;  /* the Weiszfeld iterations R, 1 .. FLTEE_GMED_MAX_ITERS */
+    double gmed_nu;     /* the smoothing floor nu: a finite value above 0 */
+} fltee_device_opts_gmed;
 
 /* Aggregate n clients x k records (8 B each: u32 LE idx, f32 LE val),
  * client-major, into d_out[d] (overwritten, or accumulated with
@@ -640,6 +699,35 @@ fltee_status_t fltee_krum_select_device(const void *d_records, size_t n, size_t 
  * the one-GPU bits.  Nothing new is revealed: the launch shapes depend on (n', d) and the
  * buffers' alignment; the keep set is never read back. */
 void fltee_set_dense_krum(uint32_t f, uint32_t m);
+
+/* ---- robust aggregation: the geometric median behind the ECALL --------------------------------
+ * Multi-Krum is a hard selection: it needs a guess of f and drops n - m honest updates a round.
+ * The geometric median (FLTEE_OPT_GMED above) needs no f, tolerates any minority of corrupted
+ * clients and keeps every honest client with a smooth weight. */
+/* Steps 1 - 5 of FLTEE_OPT_GMED alone, device-resident: d_records is n dense uploads of d
+ * parameters (records, or the layout opts' row flag names; FLTEE_OPT_DENSE is implied), opts is
+ * the base of a fltee_device_opts_gmed with FLTEE_OPT_GMED set (INVALID_PARAMETER without the
+ * flag) and gives gmed_iters, gmed_nu and, with FLTEE_OPT_CLIP, the bound (the other options are
+ * ignored).  Leaves the n weights alpha (f32) in d_alpha and the last iteration's n distances rho
+ * (f64; +inf for an invalid client) in d_rho, device memory both; asynchronous on `stream`.  The
+ * refusals and the scratch are those of the aggregate call on alg 3.  For tests, and for hosts
+ * that drive one process per GPU. */
+fltee_status_t fltee_gmed_weights_device(const void *d_records, size_t n, size_t d,
+                                         const fltee_device_opts *opts, float *d_alpha,
+                                         double *d_rho, void *stream);
+/* Process-wide, like fltee_set_dense_krum; (0, anything) is off and the default: every call is
+ * then launch for launch what it was.  On: an ecall_secure_aggregation call on the dense path of
+ * algs 3, 4, 5 (records or value rows; the staged and the pipelined path alike) is aggregated
+ * with FLTEE_OPT_GMED, gmed_iters = iters, gmed_nu = nu, on the n' clients actually aggregated
+ * (the survivors under FLTEE_AEAD_DROP); the DP noise is divided by n'.  A host that switched the
+ * geometric median on never gets a plain mean back: what cannot be answered ends with 0x2, with
+ * the existing 0x2 refusals — algs 1, 2, 6 and 7, a sparse upload, alg 5 under
+ * fltee_set_path_oram_tree(1), n > FLTEE_KRUM_MAX_N, iters > FLTEE_GMED_MAX_ITERS, a nu that is
+ * not a finite value above 0, fltee_set_dense_trim or fltee_set_dense_krum on at the same time,
+ * and a dense-sized records upload out of position.  On an eid over several GPUs the root runs
+ * the call: the one-GPU bits.  Nothing new is revealed: the launch shapes depend on (n', d, iters)
+ * and the buffers' alignment; the weights are never read back. */
+void fltee_set_dense_gmed(uint32_t iters, double nu);
 
 /* ---- authenticated uploads: AES-128-GCM (NIST SP 800-38D), 96-bit IV, 128-bit tag ------
  * Per client: K = the session key, H = E_K(0^128), J0 = IV || 0x00000001, keystream block
