@@ -209,6 +209,25 @@ hipError_t launch_krum_accumulate(const void *in, bool packed, size_t n, size_t 
 double *krum_gram(void *scratch, const KrumGeom &g);
 hipError_t launch_krum_gram(const void *in, bool packed, size_t n, size_t d, const float *client_coef, void *scratch,
                             uint32_t *status, hipStream_t s);
+// The same Gram matrix over column ranges cut on chunk boundaries (a multi-GPU eid's ranks,
+// fltee_krum_gram_ranges_device): range i of `ranks` is columns [krum_cut(g, d, ranks, i),
+// krum_cut(g, d, ranks, i + 1)) — whole chunks of g = krum_geometry(n, d), possibly none.
+// gram_range: the kernels of launch_krum_gram on one range (in: its first column of client 0,
+// stride bytes between clients, cols columns in chunks > 0 chunks of g.chunk_cols; a records range
+// holds range-local indices) into part (chunks x NP x NP doubles).  reduce_carry: the range's leg
+// of the chain: sum (NP x NP) = carry (the sum of the ranges before it; null: +0.0) with the
+// range's chunks added in ascending order.  The last range's sum is launch_krum_gram's G bit for bit.
+// rank: Krum's steps 2 - 4 on the G already in a scratch of krum_scratch_bytes(n, d).
+static inline size_t krum_cut(const KrumGeom &g, size_t d, size_t ranks, size_t i) {
+    const size_t c = g.chunks * i / ranks * g.chunk_cols;
+    return c < d ? c : d;
+}
+hipError_t launch_krum_gram_range(const void *in, bool packed, size_t stride, size_t n, size_t cols, const KrumGeom &g,
+                                  size_t chunks, const float *client_coef, double *part, uint32_t *status,
+                                  hipStream_t s);
+hipError_t launch_krum_reduce_carry(const double *part, size_t np, size_t chunks, const double *carry, double *sum,
+                                    hipStream_t s);
+hipError_t launch_krum_rank(size_t n, size_t d, size_t f, size_t m, void *scratch, hipStream_t s);
 
 // k_gmed.hip: the geometric median (smoothed Weiszfeld, FLTEE_OPT_GMED) of n dense uploads,
 // n <= FLTEE_KRUM_MAX_N, iterated on Krum's Gram matrix.  scratch_bytes: Krum's partials and G,
@@ -223,6 +242,8 @@ double *gmed_rho(void *scratch, size_t n, size_t d);
 uint32_t *gmed_valid(void *scratch, size_t n, size_t d);
 hipError_t launch_gmed_weights(const void *in, bool packed, size_t n, size_t d, size_t iters, double nu,
                                const float *client_coef, void *scratch, uint32_t *status, hipStream_t s);
+// iterate: steps 2 - 5 on the G already in a scratch of gmed_scratch_bytes(n, d)
+hipError_t launch_gmed_iterate(size_t n, size_t d, size_t iters, double nu, void *scratch, hipStream_t s);
 hipError_t launch_gmed_accumulate(const void *in, bool packed, size_t n, size_t d, const float *alpha,
                                   const uint32_t *valid, float *out, const float *client_coef, bool accumulate,
                                   hipStream_t s);

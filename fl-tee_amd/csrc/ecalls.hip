@@ -850,12 +850,26 @@ extern "C" fltee_status_t ecall_secure_aggregation(
     bool verdict_stored = false;
     bool group_tried = false;  // a shape the group declined (or failed on) is not offered to it again
     const bool tree = ecall_takes_tree(aggregation_alg, n, rpa, d);
-    // (a packed, bf16 or fp8 call is loaded on the root: the dense group path shards records by column;
-    // a trimmed call too — it needs every client's value of a column in one place, which a
-    // column shard has, but the group's per-rank sums are untrimmed: the root runs it)
-    // (a Multi-Krum call likewise: the selection needs whole clients)
-    // (a geometric-median call too: its weights need whole clients)
-    if (G && flat && !tree && !fmt && !trim_pm && !krum_on && !gmed_on && rpc == d && bpc == d * 8 + tagb) {
+    // (a packed, bf16 or fp8 call is loaded on the root: the dense group path shards records by
+    // column, under the robust switches too)
+    // Under fltee_set_dense_trim / _krum / _gmed the ranks aggregate their columns by the call's
+    // one-GPU route: a trimmed column needs no other; Multi-Krum and the geometric median share one
+    // Gram matrix, added up over the ranks in the one-GPU order, and the root's selection on it.
+    // The refusals above came first, and what the root's plan would still refuse (a shape past
+    // the 32-bit positions) is left to the root; n' = n in the group (a failing verdict under
+    // REPORT / DROP leaves for the root below)
+    GroupRobust rb;
+    if (const size_t t = trim_count(n, trim_pm))
+        rb.kind = t > FLTEE_TRIM_MAX ? GroupRobust::kTrimSelect : GroupRobust::kTrim, rb.trim = t;
+    if (krum_on) rb.kind = GroupRobust::kKrum, rb.krum_f = g_dense_krum_f, rb.krum_m = g_dense_krum_m;
+    if (gmed_on) rb.kind = GroupRobust::kGmed, rb.gmed_iters = g_dense_gmed_iters, rb.gmed_nu = g_dense_gmed_nu;
+    // aggregate()'s divisor: the n - 2 t clients a trimmed mean keeps, Multi-Krum's m (the
+    // geometric median's weights sum to one: its accumulate takes no factor)
+    const float group_coef = rb.trim ? 1.0f / (float)(n - 2 * rb.trim) : krum_on ? 1.0f / (float)g_dense_krum_m : coef;
+    if (G && flat && !tree && !fmt && rpc == d && bpc == d * 8 + tagb &&
+        (rb.kind == GroupRobust::kPlain ||
+         plan_status(aggregation_alg, n, rpc, d,
+                     ecall_opts(aggregation_alg, n, rpc, d, k_req, 0, 0, 0, trim_count(n, trim_pm))) == FLTEE_SUCCESS)) {
         // dense uploads over a multi-GPU eid: every GPU loads and decrypts its own
         // parameter range (group.hip); "Loading" = the parallel H2D, "Decryption" = the
         // decrypt + aggregate + gather.  Authenticated: every GPU also hashes its range, the
@@ -863,10 +877,10 @@ extern "C" fltee_status_t ecall_secure_aggregation(
         std::vector<uint32_t> rk;
         if (!aead) client_round_keys(client_ids, n, rk);
         st = group_dense_ecall(G, aead ? (const uint32_t *)gkeys.data() : rk.data(), n,
-                               encrypted_parameters_data, d, coef, d_out,
+                               encrypted_parameters_data, d, group_coef, d_out,
                                &execution_time_results[0], &execution_time_results[1],
                                false,  // out of position: the root's sparse rerun, every alg
-                               aead ? &gh : nullptr);
+                               aead ? &gh : nullptr, rb);
         t2 = now_s();
         if (st == FLTEE_ERROR_MAC_MISMATCH && keepv) {
             st = FLTEE_GROUP_FALLBACK;

@@ -926,6 +926,47 @@ extern "C" fltee_status_t fltee_krum_select_device(const void *d_records, size_t
     return krum_select(d_records, n, d, o, d_scores, d_keep, s, status);
 }
 
+extern "C" fltee_status_t fltee_krum_gram_ranges_device(const void *d_in, int packed, size_t n, size_t d,
+                                                        uint32_t ranks, double *d_G_out) {
+    std::lock_guard<std::recursive_mutex> lk(api_mutex());
+    // host arithmetic, before any launch
+    if (!d_in || !d_G_out || ranks == 0 || ranks > (uint32_t)kMaxDevices || n == 0 || n > FLTEE_KRUM_MAX_N ||
+        d >= ((size_t)1 << 31))
+        return FLTEE_ERROR_INVALID_PARAMETER;
+    DeviceCtx *c = current_ctx();
+    if (!c) return FLTEE_ERROR_UNEXPECTED;
+    const KrumGeom g = krum_geometry(n, d);
+    // the largest range's partials and the running sum fit the one-GPU call's scratch
+    if (!c->ws_mat.reserve(krum_scratch_bytes(n, d))) return FLTEE_ERROR_OUT_OF_MEMORY;
+    c->mat_clean = 0;
+    void *ws = c->ws_mat.ptr;
+    double *sum = krum_gram(ws, g);
+    hipStream_t s = nullptr;
+    if (fl_memset_async(c->status, 0, 4, s) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+    hipError_t e = hipSuccess;
+    if (ranks == 1 || d == 0) {
+        e = launch_krum_gram(d_in, packed != 0, n, d, nullptr, ws, c->status, s);
+    } else {
+        const size_t unit = packed ? 4 : 8;
+        const size_t stride = packed ? RowF32::row_stride(d) * 4 : d * 8;
+        bool first = true;
+        for (uint32_t i = 0; i < ranks && e == hipSuccess; ++i) {
+            const size_t lo = krum_cut(g, d, ranks, i), hi = krum_cut(g, d, ranks, i + 1);
+            if (hi == lo) continue;  // a range without chunks: skipped in the chain
+            // (a range's kernels compare idx with range-local positions, as a rank's slice holds
+            // them; these rows hold the whole call's: the order flag goes to a scratch word)
+            const size_t lc = (hi - lo + g.chunk_cols - 1) / g.chunk_cols;
+            e = launch_krum_gram_range((const uint8_t *)d_in + lo * unit, packed != 0, stride, n, hi - lo, g, lc,
+                                       nullptr, (double *)ws, lo ? c->status + 32 : c->status, s);
+            if (e == hipSuccess)
+                e = launch_krum_reduce_carry((const double *)ws, g.np, lc, first ? nullptr : sum, sum, s);
+            first = false;
+        }
+    }
+    if (e == hipSuccess) e = fl_memcpy_async(d_G_out, sum, g.np * g.np * 8, hipMemcpyDeviceToDevice, s);
+    return e == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+}
+
 extern "C" fltee_status_t fltee_gmed_weights_device(const void *d_records, size_t n, size_t d,
                                                     const fltee_device_opts *opts, float *d_alpha,
                                                     double *d_rho, void *stream) {

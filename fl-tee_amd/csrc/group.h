@@ -24,6 +24,15 @@ struct GcmHost {
     size_t aad_len = 0;
 };
 
+// What a dense group call computes from the ranks' decrypted columns (group_dense_ecall's rb)
+struct GroupRobust {
+    enum Kind : uint32_t { kPlain, kTrim, kTrimSelect, kKrum, kGmed } kind = kPlain;
+    size_t trim = 0;               // kTrim, kTrimSelect: t >= 1
+    size_t krum_f = 0, krum_m = 0;
+    size_t gmed_iters = 0;
+    double gmed_nu = 0.0;
+};
+
 // dense uploads straight from the host ciphertext, parameter-range sharded; rk_host =
 // the n clients' AES round keys (44 words each); d_out_root gets the averaged f32[d].
 // A record out of position: reject_order (baseline / path_oram, fixed cost) -> 0x2, else
@@ -32,9 +41,18 @@ struct GcmHost {
 // the GCM counters and hashes them as a window of the slices (k_ghash.hip); the root takes
 // the tags, XORs the ranks' partials and finishes; one auth word is read, and only then is
 // any rank's accumulate launched: FLTEE_ERROR_MAC_MISMATCH otherwise.
+// rb (the robust switches; the default is the plain mean, launch for launch what it was): after
+// the same load, decrypt and verdict every rank runs the call's one-GPU route on its columns — the
+// trimmed mean (kTrim: the list kernel, kTrimSelect: the selection kernel, trim = t clients a
+// side), or under kKrum / kGmed the columns are cut on the Gram pass's chunk boundaries, the
+// ranks' Gram partials are added by a carry chain in the one-GPU order, the root selects on G and
+// sends the keep (alpha, valid) words to the ranks, which sum their columns.  Nothing reads a
+// plaintext value before the verdict.  A record out of position then ends the call with 0x2
+// whatever reject_order says (the sparse rerun would be a plain mean).
 uint32_t group_dense_ecall(Group *G, const uint32_t *rk_host, size_t n, const uint8_t *enc,
                            size_t d, float coef, float *d_out_root, float *t_load, float *t_dec,
-                           bool reject_order, const GcmHost *gcm = nullptr);
+                           bool reject_order, const GcmHost *gcm = nullptr,
+                           const GroupRobust &rb = GroupRobust());
 // Where the client-major n x k records come from: decrypted into the root device's HBM
 // (root_rec), or the host ciphertext (enc, bpc bytes per client, rk = the clients' round
 // keys): then every GPU of the eid copies and decrypts the clients covering its own

@@ -13,6 +13,14 @@
 //     decrypts it with the counter offset of the slice, sums the n clients in order
 //     (the single-GPU kernel on slice-local positions) and sends its averaged slice to
 //     the root (RCCL).  Bit-identical to one GPU: each output is the same in-order sum.
+//     Under the robust switches (GroupRobust; records uploads) the same load, decrypt and verify,
+//     then instead of the plain sum: the trimmed mean of the rank's columns (list or selection
+//     kernel; columns are independent); or, for Multi-Krum and the geometric median, columns cut
+//     on the Gram pass's chunk boundaries, every rank's Gram kernels on its chunks, a carry chain
+//     rank after rank that adds the chunks' partials in the one-GPU order (NP x NP f64 a hop), the
+//     selection / the iterations on the root's G, the n keep words (alpha and valid words) to every
+//     rank device to device, and the kept / weighted in-order sums of the rank's columns.
+//     Bit-identical to one GPU.  Packed, bf16 and fp8 uploads stay on the root.
 //   advanced (alg 1): POSITION-RANGE sharding of the padded array (Option B): the
 //     reference's bitonic network run distributed (range sorts; per stage two RCCL
 //     all-to-alls transpose the rank bits into the range so its cross-range steps run
@@ -67,6 +75,9 @@ struct Rank {
     // authenticated uploads: H || E_K(J0) and the AAD of the rank's clients, the powers of H,
     // the GHASH partials, the fail words (the auth word behind them)
     Buffer gsub, gpow, gpart, gfail;
+    // Multi-Krum / geometric median: the rank's chunk partials with the chain's running sum behind
+    // them, the sum received from the rank before, the keep (alpha, valid) words from the root
+    Buffer gram, carry, sel;
 };
 
 struct Group {
@@ -75,6 +86,7 @@ struct Group {
     std::vector<Rank> r;
     Buffer rows;                    // root: W x d reduce rows (virtual ranks) / alg-6 batch rows
     Buffer gparts, gtags;           // root: the ranks' GHASH partials (W x n x P x 16), the n tags
+    Buffer robust;                  // root: Krum's / the geometric median's scratch from (n, d), G in it
     uint32_t *host = nullptr;       // pinned readback words
 };
 
@@ -148,6 +160,8 @@ Group *group_create(const int *devs, int n, uint32_t *status) {
         Rank &R = G->r[i];
         R.dev = devs[i];
         if (hipSetDevice(R.dev) != hipSuccess || !device_ctx(R.dev)) { group_free(G); return nullptr; }
+        // (what ws_mat holds on one GPU: the same bit of fltee_debug_scratch_grown)
+        R.gram.grow_bit = R.carry.grow_bit = R.sel.grow_bit = 1u << kWsMat;
         if (G->rccl || i == 0) {
             if (hipStreamCreateWithFlags(&R.s, hipStreamNonBlocking) != hipSuccess) { group_free(G); return nullptr; }
         } else {
@@ -165,6 +179,7 @@ Group *group_create(const int *devs, int n, uint32_t *status) {
         }
         for (int i = 0; i < n; ++i) G->r[i].comm = comms[i];
     }
+    G->robust.grow_bit = 1u << kWsMat;
     (void)hipSetDevice(devs[0]);
     if (hipHostMalloc((void **)&G->host, 64 * 8, hipHostMallocDefault) != hipSuccess) {
         G->host = nullptr;
@@ -186,7 +201,7 @@ static void group_free(Group *G) {
         if (R.s && (G->rccl || i == 0)) (void)fl_stream_sync(R.s);
         for (Buffer *b : {&R.cipher, &R.rec, &R.rk, &R.out, &R.chunk, &R.spare, &R.fold, &R.fold_dst,
                           &R.cbuf, &R.ctmp, &R.lap, &R.list, &R.cnt, &R.st, &R.gsub, &R.gpow, &R.gpart,
-                          &R.gfail})
+                          &R.gfail, &R.gram, &R.carry, &R.sel})
             b->release();
         if (R.comm) (void)rccl()->CommDestroy(R.comm);
         R.comm = nullptr;
@@ -197,6 +212,7 @@ static void group_free(Group *G) {
         G->rows.release();
         G->gparts.release();
         G->gtags.release();
+        G->robust.release();
         if (G->host) (void)hipHostFree(G->host);
         G->host = nullptr;
     }
@@ -450,16 +466,108 @@ static uint32_t group_records(Group &G, const GroupInput &in, size_t n, size_t r
 }
 
 // ================================================================ dense =====
+// Multi-Krum / the geometric median over the ranks' decrypted column slices (R.rec: n x dg
+// records with slice-local indices; p: the cuts, on the chunk boundaries of geom =
+// krum_geometry(n, d)).  One Gram matrix in the one-GPU summation order:
+//   every rank with chunks: the Gram kernels on its slice, its local chunk count in the grid;
+//   the carry chain, in rank order: the running NP x NP f64 sum of the ranks before (p2p: RCCL,
+//     or a device copy between virtual ranks; NP^2 * 8 bytes a hop), then the rank's chunks added
+//     to it in ascending order (krum_reduce_carry_kernel) — rank 0 from +0.0, a rank without
+//     chunks skipped;
+//   the last sum to the root's scratch as G; there the one-GPU selection (scores and ranks, or
+//     init and the R iterations) with its scratch sized from (n, d);
+//   the n keep words (alpha and valid words) to every other rank with columns, device to device.
+// sel[i]: the words rank i's accumulate reads.  Launch shapes: (n, d, W, R) and alignment alone.
+static uint32_t group_gram_select(Group &G, const std::vector<size_t> &p, size_t n, size_t d, const KrumGeom &geom,
+                                  const GroupRobust &rb, std::vector<const uint32_t *> &sel) {
+    const int W = G.W;
+    const bool krum = rb.kind == GroupRobust::kKrum;
+    const size_t cells = geom.np * geom.np;
+    Rank &R0 = G.r[0];
+    if (!reserve_on(R0, G.robust, krum ? krum_scratch_bytes(n, d) : gmed_scratch_bytes(n, d)))
+        return FLTEE_ERROR_OUT_OF_MEMORY;
+    void *ws = G.robust.ptr;
+    double *Groot = krum_gram(ws, geom);
+    auto chunks_of = [&](int i) { return (p[i + 1] - p[i] + geom.chunk_cols - 1) / geom.chunk_cols; };
+    for (int i = 0; i < W; ++i) {
+        const size_t lc = chunks_of(i);
+        if (lc == 0) continue;
+        Rank &R = G.r[i];
+        if (!reserve_on(R, R.gram, (lc + 1) * cells * 8) || !reserve_on(R, R.carry, cells * 8))
+            return FLTEE_ERROR_OUT_OF_MEMORY;
+    }
+    // (the ranks' Gram kernels run side by side: all enqueued before any rank waits for its carry)
+    for (int i = 0; i < W; ++i) {
+        const size_t lc = chunks_of(i), dg = p[i + 1] - p[i];
+        if (lc == 0) continue;
+        Rank &R = G.r[i];
+        if (hipSetDevice(R.dev) != hipSuccess ||
+            launch_krum_gram_range(R.rec.ptr, false, dg * 8, n, dg, geom, lc, nullptr, (double *)R.gram.ptr,
+                                   (uint32_t *)R.st.ptr, R.s) != hipSuccess)
+            return FLTEE_ERROR_UNEXPECTED;
+    }
+    int prev = -1;
+    const double *prev_sum = nullptr;
+    for (int i = 0; i < W; ++i) {
+        const size_t lc = chunks_of(i);
+        if (lc == 0) continue;
+        Rank &R = G.r[i];
+        double *part = (double *)R.gram.ptr, *sum = part + lc * cells;
+        if (prev >= 0 && p2p(G, {{prev, i, prev_sum, R.carry.ptr, cells * 8}}) != hipSuccess)
+            return FLTEE_ERROR_UNEXPECTED;
+        if (hipSetDevice(R.dev) != hipSuccess ||
+            launch_krum_reduce_carry(part, geom.np, lc, prev >= 0 ? (const double *)R.carry.ptr : nullptr, sum,
+                                     R.s) != hipSuccess)
+            return FLTEE_ERROR_UNEXPECTED;
+        prev = i, prev_sum = sum;
+    }
+    if (prev < 0) return FLTEE_ERROR_UNEXPECTED;  // (d > 0: some rank has a chunk)
+    if (p2p(G, {{prev, 0, prev_sum, Groot, cells * 8}}) != hipSuccess ||
+        hipSetDevice(R0.dev) != hipSuccess)
+        return FLTEE_ERROR_UNEXPECTED;
+    const uint32_t *words;
+    size_t nwords;
+    if (krum) {
+        if (launch_krum_rank(n, d, rb.krum_f, rb.krum_m, ws, R0.s) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
+        words = krum_keep(ws, n, d), nwords = n;
+    } else {
+        if (launch_gmed_iterate(n, d, rb.gmed_iters, rb.gmed_nu, ws, R0.s) != hipSuccess)
+            return FLTEE_ERROR_UNEXPECTED;
+        // NP alpha (f32), then NP valid words: one run of the scratch
+        words = (const uint32_t *)gmed_alpha(ws, n, d), nwords = 2 * geom.np;
+    }
+    std::vector<P2P> bcast;
+    for (int i = 0; i < W; ++i) {
+        sel[i] = words;
+        if (i == 0 || p[i + 1] == p[i]) continue;
+        Rank &R = G.r[i];
+        if (!reserve_on(R, R.sel, nwords * 4)) return FLTEE_ERROR_OUT_OF_MEMORY;
+        sel[i] = (const uint32_t *)R.sel.ptr;
+        bcast.push_back({0, i, words, R.sel.ptr, nwords * 4});
+    }
+    return p2p(G, bcast) == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+}
+
 // Parameter-range shard of dense uploads, straight from the host ciphertext.
 uint32_t group_dense_ecall(Group *Gp, const uint32_t *rk_host, size_t n, const uint8_t *enc,
                            size_t d, float coef, float *d_out_root, float *t_load, float *t_dec,
-                           bool reject_order, const GcmHost *gcm) {
+                           bool reject_order, const GcmHost *gcm, const GroupRobust &rb) {
     Group &G = *Gp;
     const int W = G.W;
-    if (gcm && d == 0) return FLTEE_GROUP_FALLBACK;  // no rank has a window: the root's call
+    const bool robust = rb.kind != GroupRobust::kPlain;
+    // Multi-Krum / the geometric median: the ranks share one Gram matrix
+    const bool gram = rb.kind == GroupRobust::kKrum || rb.kind == GroupRobust::kGmed;
+    if ((gcm || robust) && d == 0) return FLTEE_GROUP_FALLBACK;  // no rank has a window: the root's call
+    if (gram && (n == 0 || n > FLTEE_KRUM_MAX_N)) return FLTEE_ERROR_INVALID_PARAMETER;  // (refused before)
+    if (robust) reject_order = true;  // (the sparse rerun would be a plain mean: 0x2, as on one GPU)
+    const KrumGeom geom = gram ? krum_geometry(n, d) : KrumGeom{};
     std::vector<size_t> p(W + 1);
     // multiples of 4: whole 16-B AES blocks, 16-B aligned output slices
     for (int i = 0; i <= W; ++i) p[i] = (d * (size_t)i / (size_t)W) & ~(size_t)3;
+    // the Gram matrix's summation order is fixed by the chunks of the whole d: cuts on chunk
+    // boundaries (multiples of 16 columns), rank i the chunks [chunks i / W, chunks (i + 1) / W)
+    if (gram)
+        for (int i = 0; i <= W; ++i) p[i] = krum_cut(geom, d, (size_t)W, (size_t)i);
     p[W] = d;
     const size_t ctb = d * 8, bpc = ctb + (gcm ? FLTEE_GCM_TAG_BYTES : 0);  // the host stride
     // authenticated: the ranks' partial vectors (n x P x 16 bytes each) meet on the root, one
@@ -511,6 +619,7 @@ uint32_t group_dense_ecall(Group *Gp, const uint32_t *rk_host, size_t n, const u
     auto t1 = std::chrono::steady_clock::now();
     if (t_load) *t_load = std::chrono::duration<float>(t1 - t0).count();
     std::vector<P2P> gather;
+    std::vector<const uint32_t *> sel_words(W, nullptr);  // Krum's keep / the median's alpha, valid words
     auto accumulate = [&](int i) -> uint32_t {  // rank i's columns of the n clients, in order
         Rank &R = G.r[i];
         const size_t dg = p[i + 1] - p[i];
@@ -520,8 +629,27 @@ uint32_t group_dense_ecall(Group *Gp, const uint32_t *rk_host, size_t n, const u
             o = (float *)R.out.ptr;
             gather.push_back({i, 0, o, d_out_root + p[i], dg * 4});
         }
-        return launch_dense_accumulate(R.rec.ptr, n, dg, coef, o, nullptr, false, (uint32_t *)R.st.ptr,
-                                       R.s) == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
+        uint32_t *st = (uint32_t *)R.st.ptr;
+        hipError_t e = hipSuccess;
+        switch (rb.kind) {  // the one-GPU launcher of the call's route, on the rank's n x dg slice
+        case GroupRobust::kPlain:
+            e = launch_dense_accumulate(R.rec.ptr, n, dg, coef, o, nullptr, false, st, R.s);
+            break;
+        case GroupRobust::kTrim:
+            e = launch_trimmed_mean(R.rec.ptr, false, n, dg, rb.trim, coef, o, nullptr, false, st, R.s);
+            break;
+        case GroupRobust::kTrimSelect:
+            e = launch_trim_select(R.rec.ptr, false, n, dg, rb.trim, coef, o, nullptr, false, st, R.s);
+            break;
+        case GroupRobust::kKrum:  // (sel: the root's words, or this rank's copy of them)
+            e = launch_krum_accumulate(R.rec.ptr, false, n, dg, sel_words[i], coef, o, nullptr, false, R.s);
+            break;
+        case GroupRobust::kGmed:
+            e = launch_gmed_accumulate(R.rec.ptr, false, n, dg, (const float *)sel_words[i],
+                                       sel_words[i] + geom.np, o, nullptr, false, R.s);
+            break;
+        }
+        return e == hipSuccess ? FLTEE_SUCCESS : FLTEE_ERROR_UNEXPECTED;
     };
     for (int i = 0; i < W; ++i) {
         Rank &R = G.r[i];
@@ -532,6 +660,7 @@ uint32_t group_dense_ecall(Group *Gp, const uint32_t *rk_host, size_t n, const u
         if (launch_aes_ctr_slice((const uint8_t *)R.cipher.ptr, n, dg * 8, dg, (const uint32_t *)R.rk.ptr,
                                  (uint8_t *)R.rec.ptr, p[i] / 2, (uint32_t)p[i], R.s) != hipSuccess)
             return FLTEE_ERROR_UNEXPECTED;
+        if (gram) continue;  // (every rank's Gram pass comes first)
         if (uint32_t st = accumulate(i)) return st;
     }
     if (gcm) {
@@ -579,12 +708,16 @@ uint32_t group_dense_ecall(Group *Gp, const uint32_t *rk_host, size_t n, const u
             if (t_dec) *t_dec = std::chrono::duration<float>(std::chrono::steady_clock::now() - t1).count();
             return FLTEE_ERROR_MAC_MISMATCH;
         }
+    }
+    // (authenticated: past the verdict — the Gram pass reads plaintext values too)
+    if (gram)
+        if (uint32_t st = group_gram_select(G, p, n, d, geom, rb, sel_words)) return st;
+    if (gcm || gram)
         for (int i = 0; i < W; ++i) {
             if (p[i + 1] == p[i]) continue;
             if (hipSetDevice(G.r[i].dev) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
             if (uint32_t st = accumulate(i)) return st;
         }
-    }
     if (p2p(G, gather) != hipSuccess) return FLTEE_ERROR_UNEXPECTED;
     std::vector<const uint32_t *> sw;
     for (int i = 0; i < W; ++i) sw.push_back((const uint32_t *)G.r[i].st.ptr);

@@ -196,8 +196,17 @@ hipError_t launch_gmed_weights(const void *in, bool packed, size_t n, size_t d, 
     if (n == 0 || n > FLTEE_KRUM_MAX_N || iters == 0 || iters > FLTEE_GMED_MAX_ITERS || !(nu > 0.0) ||
         !(nu < __builtin_inf()))
         return hipErrorInvalidValue;
-    const KrumGeom g = krum_geometry(n, d);
     if (hipError_t e = launch_krum_gram(in, packed, n, d, client_coef, scratch, status, s)) return e;
+    return launch_gmed_iterate(n, d, iters, nu, scratch, s);
+}
+
+// steps 2 - 5 on the G in the scratch (krum_gram(scratch, krum_geometry(n, d))): valid, the
+// iterations and alpha, where gmed_alpha / gmed_rho / gmed_valid find them
+hipError_t launch_gmed_iterate(size_t n, size_t d, size_t iters, double nu, void *scratch, hipStream_t s) {
+    if (n == 0 || n > FLTEE_KRUM_MAX_N || iters == 0 || iters > FLTEE_GMED_MAX_ITERS || !(nu > 0.0) ||
+        !(nu < __builtin_inf()))
+        return hipErrorInvalidValue;
+    const KrumGeom g = krum_geometry(n, d);
     const double *G = krum_gram(scratch, g);
     double *w = gmed_w(scratch, g), *u = gmed_u(scratch, g), *rho = gmed_rho(scratch, n, d);
     float *alpha = gmed_alpha(scratch, n, d);

@@ -34,6 +34,12 @@
 //       adjacent outputs and adds keep ? x : +0.0 in upload order (a select, never a product:
 //       a dropped NaN or inf reaches no sum), then k_rows.hip's epilogue (coef, or out +=).
 //
+//   krum_reduce_carry_kernel  the same sum as a leg of a chain over column ranges cut on chunk
+//       boundaries (launch_krum_gram_range: a multi-GPU eid's ranks, fltee_krum_gram_ranges_device):
+//       a range's chunks added, in ascending order, onto the running sum of the ranges before it
+//       (the first range: +0.0) — the additions of krum_reduce_kernel, one after the other, on
+//       whichever device holds the chunk.
+//
 // Every value is read at a fixed address, twice (the Gram pass re-reads a macro-tile's rows
 // once per partner macro-tile above 128 clients); every loop bound and grid is a function of
 // (n, d) and the pointers' alignment; q and m are compare constants; compares feed selects and
@@ -233,6 +239,22 @@ __global__ __launch_bounds__(256) void krum_reduce_kernel(const double *__restri
     if ((a >> 4) != (b >> 4)) G[(size_t)b * np + a] = s;
 }
 
+// A leg of the chain: S[a][b] = ((carry[a][b] + P_0[a][b]) + P_1[a][b]) + ... over this range's chunks;
+// carry = the running sum of the ranges before it (null: +0.0, the first range).  Every leg mirrors
+// its tile pairs, so S is a whole matrix wherever the chain ends.  S may be carry (a cell is read
+// and written by one lane; the mirrored cells are read by none).
+__global__ __launch_bounds__(256) void krum_reduce_carry_kernel(const double *__restrict__ part, uint32_t np,
+                                                                uint32_t chunks, const double *carry, double *S) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, cells = (size_t)np * np;
+    if (i >= cells) return;
+    const uint32_t a = (uint32_t)(i / np), b = (uint32_t)(i % np);
+    if ((a >> 4) > (b >> 4)) return;
+    double s = carry ? carry[i] : 0.0;
+    for (uint32_t c = 0; c < chunks; ++c) s = __dadd_rn(s, part[(size_t)c * cells + i]);
+    S[i] = s;
+    if ((a >> 4) != (b >> 4)) S[(size_t)b * np + a] = s;
+}
+
 // ---- step 2, 3: distances and scores ----------------------------------------------------------
 __global__ __launch_bounds__(1024) void krum_score_kernel(const double *__restrict__ G, uint32_t np, uint32_t n,
                                                           uint32_t q, double *__restrict__ scores) {
@@ -365,15 +387,53 @@ hipError_t launch_krum_gram(const void *in, bool packed, size_t n, size_t d, con
     return hipGetLastError();
 }
 
-hipError_t launch_krum_select(const void *in, bool packed, size_t n, size_t d, size_t f, size_t m,
-                              const float *client_coef, void *scratch, uint32_t *status, hipStream_t s) {
-    // (the plan refuses these)
-    if (n > FLTEE_KRUM_MAX_N || n < 2 * f + 3 || m == 0 || m > n - f || d >= ((size_t)1 << 31))
+// The Gram pass of a column range cut on chunk boundaries.  g: the geometry of the WHOLE call,
+// krum_geometry(n, d) — the chunk length and NP; in: the range's first column of client 0, stride:
+// bytes between clients (a rank's own n x cols slice, or a range of whole rows), cols: the range's
+// columns, chunks = ceil(cols / g.chunk_cols) > 0 of them; part: chunks x NP x NP doubles.  The
+// kernels and the k-step order inside a chunk are launch_krum_gram's.  A records range holds
+// range-local indices (idx == column - first column).
+hipError_t launch_krum_gram_range(const void *in, bool packed, size_t stride, size_t n, size_t cols, const KrumGeom &g,
+                                  size_t chunks, const float *client_coef, double *part, uint32_t *status,
+                                  hipStream_t s) {
+    if (n == 0 || n > FLTEE_KRUM_MAX_N || cols >= ((size_t)1 << 31) || chunks == 0 ||
+        chunks != (cols + g.chunk_cols - 1) / g.chunk_cols || g.np != (n + 15) / 16 * 16)
         return hipErrorInvalidValue;
+    KrumGeom r = g;
+    r.chunks = chunks;  // (the grid's y; the kernels take the chunk length and the range's columns)
+    const uintptr_t a = (uintptr_t)in;
+    // the load widths of launch_krum_gram, with every row's start as aligned as the first
+    if (packed) {
+        if (a % 16 == 0 && stride % 16 == 0) launch_gram<true, 4>(in, stride, n, cols, r, client_coef, part, status, s);
+        else if (a % 8 == 0 && stride % 8 == 0) launch_gram<true, 2>(in, stride, n, cols, r, client_coef, part, status, s);
+        else launch_gram<true, 1>(in, stride, n, cols, r, client_coef, part, status, s);
+    } else {
+        if (a % 16 == 0 && stride % 16 == 0 && cols % 2 == 0)
+            launch_gram<false, 2>(in, stride, n, cols, r, client_coef, part, status, s);
+        else launch_gram<false, 1>(in, stride, n, cols, r, client_coef, part, status, s);
+    }
+    return hipGetLastError();
+}
+
+// The range's leg of the chain: sum (NP x NP) = carry (the running sum of the ranges before it;
+// null: +0.0, the first range) with the range's chunks added in ascending order.  Ranges in
+// ascending order: the additions of krum_reduce_kernel one after the other, so the last range's
+// sum is launch_krum_gram's G bit for bit.
+hipError_t launch_krum_reduce_carry(const double *part, size_t np, size_t chunks, const double *carry, double *sum,
+                                    hipStream_t s) {
+    if (np == 0 || np > FLTEE_KRUM_MAX_N || chunks == 0) return hipErrorInvalidValue;
+    FLTEE_LAUNCH(krum_reduce_carry_kernel, dim3((unsigned)((np * np + 255) / 256)), dim3(256), 0, s, part,
+                 (uint32_t)np, (uint32_t)chunks, carry, sum);
+    return hipGetLastError();
+}
+
+// steps 2 - 4 on the G in the scratch (krum_gram(scratch, krum_geometry(n, d))): the scores and the
+// keep words, where krum_scores / krum_keep find them
+hipError_t launch_krum_rank(size_t n, size_t d, size_t f, size_t m, void *scratch, hipStream_t s) {
+    if (n > FLTEE_KRUM_MAX_N || n < 2 * f + 3 || m == 0 || m > n - f) return hipErrorInvalidValue;
     const KrumGeom g = krum_geometry(n, d);
     double *G = krum_gram(scratch, g), *scores = krum_scores(scratch, n, d);
     uint32_t *keep = krum_keep(scratch, n, d);
-    if (hipError_t e = launch_krum_gram(in, packed, n, d, client_coef, scratch, status, s)) return e;
     size_t P = 64;
     while (P < n) P <<= 1;
     FLTEE_LAUNCH(krum_score_kernel, dim3((unsigned)n), dim3((unsigned)P), 0, s, G, (uint32_t)g.np, (uint32_t)n,
@@ -381,6 +441,15 @@ hipError_t launch_krum_select(const void *in, bool packed, size_t n, size_t d, s
     FLTEE_LAUNCH(krum_rank_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scores, (uint32_t)n,
                  (uint32_t)m, keep);
     return hipGetLastError();
+}
+
+hipError_t launch_krum_select(const void *in, bool packed, size_t n, size_t d, size_t f, size_t m,
+                              const float *client_coef, void *scratch, uint32_t *status, hipStream_t s) {
+    // (the plan refuses these)
+    if (n > FLTEE_KRUM_MAX_N || n < 2 * f + 3 || m == 0 || m > n - f || d >= ((size_t)1 << 31))
+        return hipErrorInvalidValue;
+    if (hipError_t e = launch_krum_gram(in, packed, n, d, client_coef, scratch, status, s)) return e;
+    return launch_krum_rank(n, d, f, m, scratch, s);
 }
 
 // Fewer outputs than this: 64-lane blocks, one wave a block spread over every CU (k_trim.hip)

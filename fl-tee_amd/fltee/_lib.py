@@ -130,6 +130,7 @@ SIGNATURES = {
     "fltee_set_dense_trim": (None, [_U32]),
     "fltee_set_dense_trim_select": (None, [ctypes.c_int]),
     "fltee_krum_select_device": (_U32, [_P, _S, _S, ctypes.POINTER(DeviceOpts), _P, _P, _P]),
+    "fltee_krum_gram_ranges_device": (_U32, [_P, ctypes.c_int, _S, _S, _U32, _P]),
     "fltee_set_dense_krum": (None, [_U32, _U32]),
     "fltee_gmed_weights_device": (_U32, [_P, _S, _S, ctypes.POINTER(DeviceOpts), _P, _P, _P]),
     "fltee_set_dense_gmed": (None, [_U32, ctypes.c_double]),

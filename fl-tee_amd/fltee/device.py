@@ -112,6 +112,24 @@ def krum_select(records, n, d, f, m, stream=None, **kw):
     return scores, keep
 
 
+def krum_gram_ranges(records, n, d, ranks, packed=False):
+    """fltee_krum_gram_ranges_device: the Gram matrix of n dense uploads of d parameters (records,
+    or packed=True f32 rows) computed over `ranks` column ranges cut on the Gram pass's chunk
+    boundaries and combined by the carry chain, as an eid over `ranks` GPUs does -> G float64
+    [NP, NP], NP = 16 * ceil(n / 16), a cuda tensor: the one-GPU pass's bits for any ranks.  Runs
+    on the current device's null stream.  What the library refuses by host arithmetic (ranks
+    outside 1 .. 64, n outside 1 .. KRUM_MAX_N, d >= 2^31) raises ValueError here, before any
+    allocation."""
+    if not 1 <= ranks <= 64 or not 1 <= n <= L.KRUM_MAX_N or not 0 <= d < 1 << 31:
+        raise ValueError(f"fltee_krum_gram_ranges_device refuses n={n}, d={d}, ranks={ranks}")
+    assert records.is_cuda
+    npad = (n + 15) // 16 * 16
+    G = torch.empty((npad, npad), dtype=torch.float64, device=records.device)
+    _check(L.lib().fltee_krum_gram_ranges_device(_ptr(records), 1 if packed else 0, n, d, ranks, _ptr(G)),
+           "fltee_krum_gram_ranges_device")
+    return G
+
+
 def gmed_weights(records, n, d, iters, nu, stream=None, **kw):
     """fltee_gmed_weights_device: the geometric median's weights alone, on n dense uploads of d
     parameters (records, or packed= / bf16= / fp8= rows; clip= with clipping=) ->

@@ -656,9 +656,12 @@ size_t fltee_trim_count(size_t n, uint32_t per_mille);
  * ecall_client_size_optimized_secure_aggregation call; a dense-sized records upload out of
  * position (FLTEE_DEV_ERR_DENSE_ORDER, rerun sparse otherwise) ends with 0x2 after the one status
  * readback there already is.  Under AEAD the verification and the verdict come first, unchanged.
- * On an eid over several GPUs the dense group path declines a trimmed call and the root runs
- * it: the one-GPU bits.  Nothing new is revealed: the launch shapes depend on (n', d, t) and
- * the buffers' alignment, all public. */
+ * On an eid over several GPUs a trimmed records call takes the dense group path: every GPU
+ * loads, decrypts and (AEAD) hashes its columns as for a plain call, and after the one verdict
+ * trims its own columns — they are independent — into its slice of the output: the one-GPU
+ * bits.  (A packed, bf16 or fp8 call is loaded and run on the root, trimmed or not.)  Nothing
+ * new is revealed: the launch shapes depend on (n', d, t), the eid's size and the buffers'
+ * alignment, all public. */
 void fltee_set_dense_trim(uint32_t per_mille);
 /* Process-wide; off by default: every call is then what it is above — t > FLTEE_TRIM_MAX (the
  * median from 131 clients on) ends with 0x2.  On, under fltee_set_dense_trim: a call whose
@@ -666,7 +669,8 @@ void fltee_set_dense_trim(uint32_t per_mille);
  * FLTEE_OPT_TRIM_SELECT when the request's n <= FLTEE_TRIM_SELECT_MAX_N, and ends with 0x2 above
  * it; a call with t <= FLTEE_TRIM_MAX stays on the list kernel, launch for launch.  Everything
  * else about a trimmed call holds: n' under FLTEE_AEAD_DROP, the divisor n' - 2 t, the staged and
- * the pipelined path, the refusals, the root running a multi-GPU eid's trimmed call.  Nothing
+ * the pipelined path, the refusals, a multi-GPU eid's column shards (each runs the selection
+ * kernel on its columns).  Nothing
  * new is revealed: the launch shapes depend on (n', d) and on whether t > FLTEE_TRIM_MAX. */
 void fltee_set_dense_trim_select(int on);
 
@@ -685,6 +689,26 @@ void fltee_set_dense_trim_select(int on);
 fltee_status_t fltee_krum_select_device(const void *d_records, size_t n, size_t d,
                                         const fltee_device_opts *opts, double *d_scores,
                                         uint32_t *d_keep, void *stream);
+/* Step 1 of FLTEE_OPT_KRUM / FLTEE_OPT_GMED alone, over column ranges: the Gram matrix G = X X^T
+ * of n dense uploads of d parameters (d_in: records, or with packed != 0 f32 rows) as an eid over
+ * `ranks` GPUs computes it.  The one-GPU pass adds the partial matrices of the `chunks` column
+ * chunks of its geometry (a function of (n, d): chunks of chunk_cols columns, a multiple of 16) in
+ * ascending chunk order from +0.0.  Range i of `ranks` is the whole chunks
+ * [chunks i / ranks, chunks (i + 1) / ranks) — columns [min(c_i chunk_cols, d),
+ * min(c_(i+1) chunk_cols, d)), possibly none; each range runs the one-GPU Gram kernels on its
+ * columns, and a carry chain adds its chunks, ascending, onto the running NP x NP f64 sum of the
+ * ranges before it (the first from +0.0; a range without chunks is skipped): the additions of the
+ * one-GPU pass in their order, so G is that pass's bit for bit for any `ranks`.  Here every range
+ * runs on the current device, on its null stream, asynchronously; ranks = 1 is the one-GPU pass
+ * itself, launch for launch.  d_G_out: NP x NP doubles, NP = 16 ceil(n / 16), device memory; the
+ * entries past n are zero.  The selection-only entries above and below cover the rest of a call.
+ * Refused by host arithmetic, before any launch, with FLTEE_ERROR_INVALID_PARAMETER: ranks = 0 or
+ * above 64, n = 0 or above FLTEE_KRUM_MAX_N, d >= 2^31, a null pointer.  The records' idx ==
+ * position check reaches fltee_device_status only with ranks = 1 (a range's kernels compare with
+ * range-local positions, which an eid's ranks hold and whole rows do not).  For tests of the
+ * chain's order, and for hosts that drive one process per GPU. */
+fltee_status_t fltee_krum_gram_ranges_device(const void *d_in, int packed, size_t n, size_t d,
+                                             uint32_t ranks, double *d_G_out);
 /* Process-wide, like fltee_set_dense_trim; (0, 0) is off and the default: every call is then
  * launch for launch what it was.  On: an ecall_secure_aggregation call on the dense path of algs
  * 3, 4, 5 (a dense upload in position, records or value rows; the staged and the pipelined path
@@ -695,9 +719,14 @@ fltee_status_t fltee_krum_select_device(const void *d_records, size_t n, size_t 
  * zero-filled, the timers written, the round kept) — algs 1, 2, 6 and 7, a sparse upload, alg 5
  * under fltee_set_path_oram_tree(1), n' < 2 f + 3, m = 0, m > n' - f, n > FLTEE_KRUM_MAX_N,
  * fltee_set_dense_trim on at the same time, and a dense-sized records upload out of position.
- * On an eid over several GPUs the dense group path declines such a call and the root runs it:
- * the one-GPU bits.  Nothing new is revealed: the launch shapes depend on (n', d) and the
- * buffers' alignment; the keep set is never read back. */
+ * On an eid over several GPUs a records call is sharded by column, cut on the Gram pass's chunk
+ * boundaries: after the one verdict every GPU runs the Gram kernels on its columns, a carry chain
+ * adds the chunks' partials rank after rank in the one-GPU order (fltee_krum_gram_ranges_device
+ * above states it), the root scores and ranks on the resulting G, the n keep words go to every
+ * GPU device to device, and each sums the kept clients over its columns: the one-GPU bits.  (A
+ * packed, bf16 or fp8 call is loaded and run on the root.)  Nothing new is revealed: the launch
+ * shapes depend on (n', d), the eid's size and the buffers' alignment; the keep set is never read
+ * back. */
 void fltee_set_dense_krum(uint32_t f, uint32_t m);
 
 /* ---- robust aggregation: the geometric median behind the ECALL --------------------------------
@@ -724,9 +753,12 @@ fltee_status_t fltee_gmed_weights_device(const void *d_records, size_t n, size_t
  * the existing 0x2 refusals — algs 1, 2, 6 and 7, a sparse upload, alg 5 under
  * fltee_set_path_oram_tree(1), n > FLTEE_KRUM_MAX_N, iters > FLTEE_GMED_MAX_ITERS, a nu that is
  * not a finite value above 0, fltee_set_dense_trim or fltee_set_dense_krum on at the same time,
- * and a dense-sized records upload out of position.  On an eid over several GPUs the root runs
- * the call: the one-GPU bits.  Nothing new is revealed: the launch shapes depend on (n', d, iters)
- * and the buffers' alignment; the weights are never read back. */
+ * and a dense-sized records upload out of position.  On an eid over several GPUs a records call
+ * is sharded by column as a Multi-Krum call is: the Gram passes and their carry chain on the
+ * GPUs, the iterations on the root's G, the n weights and n valid words to every GPU device to
+ * device, the weighted sums per column slice: the one-GPU bits.  (A packed, bf16 or fp8 call is
+ * loaded and run on the root.)  Nothing new is revealed: the launch shapes depend on (n', d,
+ * iters), the eid's size and the buffers' alignment; the weights are never read back. */
 void fltee_set_dense_gmed(uint32_t iters, double nu);
 
 /* ---- authenticated uploads: AES-128-GCM (NIST SP 800-38D), 96-bit IV, 128-bit tag ------
